@@ -6,14 +6,25 @@ Metric (BASELINE.json): hashed GiB/s (device-resident) + Mobjects/s on
 synthetic bytes generated in HBM.  A step = one launch hashing the whole
 batch (every attribute of every object -> coords[n, 17]).
 
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) sets up, warms up,
+times the K steps and prints the line: the headline (`value`, `ms_per_step`)
+and the roofline figures that follow from the same steps.  `--dump-outputs
+DIR` also writes the coordinates of the last timed step (a fixed seeded
+sample of rows; inputs are the same from run to run) as DIR/*.npy.  `--full`
+adds everything else the line can carry, each measured in runs of its own
+after the headline: the streaming probe, `secondary` (configs 3b, 2, 1 and
+5), `regions`, `host_path`, `config4`, `allgather` and the CPU baselines,
+which also check the GPU's coordinates against the oracle.
+
 Multi-GPU (`--gpus N`, one rank per GPU on RCCL): launched bare, the parent
 starts N fresh rank processes itself (before it touches the GPU) and relays
 rank 0's line; under torchrun/torch.distributed.run (WORLD_SIZE set) each
 process is one rank and WORLD_SIZE must equal --gpus.  Each rank owns its own
 10M-object shard (weak scaling, no collective in the timed region); the RCCL
-all-gather of the coordinates is timed separately and reported as `allgather`.
+all-gather of the coordinates is timed separately and reported as `allgather`
+(with `--full`).
 
-Config 4 rides along in every line as `config4`: one batch
+Config 4 rides along in every `--full` line as `config4`: one batch
 of 100M config-3b objects split over the N ranks (hyperdex_amd.dist.
 shard_ranges: equal object counts when that keeps every rank within 0.1 % of
 its byte share, else byte-balanced cuts), each rank hashing its shard
@@ -25,7 +36,8 @@ config 4's strong-scaling curve.
 HDX_BENCH_DEVICE=cpu (+ HDX_BENCH_BACKEND=gloo) is a CPU rehearsal of the
 multi-rank plumbing only — launch, shard cuts, the config-4 gather and the
 JSON relay — with a stand-in that writes each object's index instead of its
-coordinates (no hashing, no throughput; `value` is null).
+coordinates (no hashing, no throughput; `value` is null).  The rehearsal has
+no headline, config 4's plumbing is all it runs, with or without `--full`.
 
 Prints ONE JSON line on rank 0.
 """
@@ -99,6 +111,13 @@ def parse_args(argv=None):
                     help="skip timing config 3b (16 mixed attrs) beside the config-3a line")
     ap.add_argument("--traffic", default=latest_traffic_file(),
                     help="HBM bytes/launch measured by scripts/gpu_profile.sh (rocprofv3 PMC)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline's timed steps, also measure everything else the line can carry: "
+                         "the streaming probe, the other configs (`secondary`), regions, the host path, "
+                         "config 4, the all-gather and the CPU baselines (each with its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's coordinates (a fixed seeded sample "
+                         "of rows) as DIR/<name>.npy")
     return ap.parse_args(argv)
 
 
@@ -198,6 +217,12 @@ def run_rank(args):
         return tuple(float(v) for v in t.tolist())
 
     cfg, n = args.config, args.objects or (50_000_000 if args.config == "cfg5" else 10_000_000)
+    if not args.full:
+        # a plain run: set up, warm up, the timed steps, --dump-outputs, the line.
+        # Everything measured beside the headline is switched off.
+        args.no_stream_probe = args.no_secondary = args.no_regions = args.no_host_path = True
+        args.no_allgather = args.no_cpu_baseline = True
+        args.config4_objects = args.cfg5_objects = 0
     stream = torch.cuda.current_stream(dev)
     if cfg == "cfg5":
         # config 5: reindex sweep over stored objects (values in the daemon's
@@ -248,6 +273,8 @@ def run_rank(args):
     elapsed = time.perf_counter() - t0
     kernel_ms = float(np.mean([s.elapsed_time(e) for s, e in ev]))
     elapsed, kernel_ms = max_over_ranks(elapsed, kernel_ms)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, coords, "coords" if world == 1 else "coords_rank%d" % rank)
 
     ms_per_step = elapsed / args.steps * 1e3
     total_payload = payload * world
@@ -270,6 +297,7 @@ def run_rank(args):
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": args.full,
         "warmup_sustained_ms": round(sustained_ms, 1),
         "ms_per_step": round(ms_per_step, 4),
         "higher_is_better": True,
@@ -877,6 +905,43 @@ def sustain(launch, stream, min_ms):
     e.record(stream)
     torch.cuda.synchronize()
     return one + (s.elapsed_time(e) if reps else 0.0)
+
+
+DUMP_SEED = 0x44554D50          # the row sample of --dump-outputs
+DUMP_BUDGET_BYTES = 48 << 20    # of the 64 MB a dump may take
+
+
+def dump_rows(n, A):
+    """The rows of an (n, A) coordinate matrix that --dump-outputs writes: all
+    of them when they fit the budget, else the first, the last and a seeded
+    sample of the others, ascending (the same rows for the same n and A)."""
+    per_row = 8 + A * (8 + 8 * 4)  # the row's index, its coordinates as float64 and as 8 float32 bytes each
+    cap = max(2, DUMP_BUDGET_BYTES // per_row)
+    if n <= cap:
+        return np.arange(n, dtype=np.int64)
+    rng = np.random.default_rng(DUMP_SEED)
+    return np.unique(np.concatenate([[0, n - 1], rng.integers(0, n, cap - 2)])).astype(np.int64)
+
+
+def write_outputs(out_dir, name, rows, values):
+    """`values` (len(rows), A) u64: the coordinates of `rows`, as
+    out_dir/<name>.npy in float64 (a u64 rounded to 53 bits: what a numeric
+    comparison wants), <name>_bytes.npy in float32 (each coordinate's 8 bytes,
+    most significant first: exact) and <name>_rows.npy (the rows' indices)."""
+    os.makedirs(out_dir, exist_ok=True)
+    v = np.ascontiguousarray(values, dtype=np.uint64)
+    np.save(os.path.join(out_dir, name + ".npy"), v.astype(np.float64))
+    b = v.astype(">u8").view(np.uint8).reshape(v.shape + (8,))
+    np.save(os.path.join(out_dir, name + "_bytes.npy"), b.astype(np.float32))
+    np.save(os.path.join(out_dir, name + "_rows.npy"), np.asarray(rows).astype(np.float64))
+
+
+def dump_outputs(out_dir, coords, name):
+    """--dump-outputs: the timed path's result (the (n, A) coordinates its last
+    step wrote on the device), rows dump_rows(n, A) of it."""
+    rows = dump_rows(*coords.shape)
+    got = coords[torch_index(rows, coords.device)].cpu().numpy().view(np.uint64)
+    write_outputs(out_dir, name, rows, got)
 
 
 def time_config(cfg, n, dev, stream, steps=10, warmup=2, warmup_ms=150.0):

@@ -7,9 +7,9 @@ set -o pipefail
 O=gpurun_out/bracket; mkdir -p $O
 X="--no-host-path --no-stream-probe --config4-objects 0 --cpu-seconds 1 --no-cpu-baseline --no-regions"
 timeout -k 10 200 python3 bench.py --config cfg3b --no-secondary $X > $O/a.json 2>/dev/null || exit 1
-timeout -k 10 300 python3 bench.py --cfg5-objects 0 $X > $O/b.json 2>/dev/null || exit 1
+timeout -k 10 300 python3 bench.py --full --cfg5-objects 0 $X > $O/b.json 2>/dev/null || exit 1
 timeout -k 10 200 python3 bench.py --config cfg3b --no-secondary $X > $O/c.json 2>/dev/null || exit 1
-timeout -k 10 300 python3 bench.py --cfg5-objects 0 $X > $O/d.json 2>/dev/null || exit 1
+timeout -k 10 300 python3 bench.py --full --cfg5-objects 0 $X > $O/d.json 2>/dev/null || exit 1
 python3 - <<'P'
 import json
 for f in "abcd":

@@ -1,8 +1,8 @@
 #!/bin/bash
 # Round evidence (run under gpurun), everything under gpurun_out/profround_TAG:
-#  1. rocprofv3 --kernel-trace --stats of the exact default command
-#     (`python3 bench.py`): its hash-kernel average must agree with the bench
-#     line's roofline.kernel_ms;
+#  1. rocprofv3 --kernel-trace --stats of the whole default line
+#     (`python3 bench.py --full`): its hash-kernel average must agree with the
+#     bench line's roofline.kernel_ms;
 #  2. per config, the bench line under --kernel-trace --stats (config 5 at
 #     BASELINE's 50 M objects);
 #  3. per config, FETCH_SIZE and WRITE_SIZE in separate --pmc runs of
@@ -19,10 +19,10 @@ cd /tmp && export TMPDIR=/tmp
 if [ "$MODE" != pmc ]; then
 echo "[$(date +%T)] default bench under kernel trace"
 timeout -k 10 500 rocprofv3 --kernel-trace --stats -d "$OUT/default_trace" -o run --output-format csv \
-    -- python3 $ROOT/bench.py > "$OUT/default_bench.json" 2> "$OUT/default_bench.err" || exit $?
+    -- python3 $ROOT/bench.py --full > "$OUT/default_bench.json" 2> "$OUT/default_bench.err" || exit $?
 for CFG in cfg3b cfg2 cfg1 cfg5 cfg5k cfg5r; do
   echo "[$(date +%T)] $CFG bench under kernel trace"
-  EXTRA="--no-secondary --no-host-path --no-stream-probe --config4-objects 0 --cpu-seconds 3"
+  EXTRA="--full --no-secondary --no-host-path --no-stream-probe --config4-objects 0 --cpu-seconds 3"
   B=$CFG
   case $CFG in cfg5k) B="cfg5 --store-layout keycol";; cfg5r) B="cfg5 --store-layout records";; esac
   timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$OUT/${CFG}_trace" -o run --output-format csv \
