@@ -4,6 +4,7 @@
 // tests run in hdx_index.hip / hdx_kernels.hip.
 #include <hip/hip_runtime.h>
 
+#include <cstdint>
 #include <cstring>
 #include <functional>
 #include <vector>
@@ -74,6 +75,7 @@ HDX_EXPORT hdx_status hdx_index_encode_device(uint32_t type, const uint8_t* blob
     }
     if (n == 0) return HDX_OK;
     if (!blob || !off || !len || !out) return fail(HDX_E_INVALID, "NULL device pointer");
+    if ((uintptr_t)out % 8) return fail(HDX_E_INVALID, "out must be 8-byte aligned");
     hdx_status st = bind_device(-1);
     if (st != HDX_OK) return st;
     IndexArgs a{};

@@ -9,7 +9,8 @@
 //           = the int64 encoding (ordered int64, NOT the calendar hash) -> 8 B
 //       index_encoding_float::encode      daemon/index_float.cc:75-90
 //           pack64be(hash(FLOAT, v)) ++ packdoublele(v or 0.0)    -> 16 B
-//     One lane per value, 8-byte loads at any alignment, 8/16-byte stores.
+//     One lane per value, 8-byte loads at any alignment, 8/16-byte stores to
+//     an 8-byte-aligned `out`.
 // (2) Search endpoints.  configuration::lookup_search
 //     (common/configuration.cc:775-858) drops a region of a subspace when a
 //     range's hashed endpoint falls outside the region's box.  One lane per
@@ -25,6 +26,9 @@ namespace hdx {
 
 typedef uint64_t __attribute__((aligned(1))) u64_u;
 typedef const __attribute__((address_space(1))) u64_u* gu64_ptr;
+// FLOAT's 16-byte key goes out as one vector store that claims only the 8-byte
+// alignment include/hdxhash.h asks of `out` (a uint64_t array works)
+typedef u64x2 __attribute__((aligned(8))) u64x2_a8;
 
 __global__ void __launch_bounds__(256) index_encode_kernel(const IndexArgs a) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -41,7 +45,7 @@ __global__ void __launch_bounds__(256) index_encode_kernel(const IndexArgs a) {
         u64x2 e;
         e.x = __builtin_bswap64(h);
         e.y = bits;  // packdoublele(number): the value's own bytes, 0.0 when empty
-        reinterpret_cast<u64x2*>(a.out)[i] = e;
+        reinterpret_cast<u64x2_a8*>(a.out)[i] = e;
     } else {
         reinterpret_cast<uint64_t*>(a.out)[i] = bad ? 0 : __builtin_bswap64(encode_int64(bits));
     }

@@ -22,7 +22,8 @@ def index_key_size(type_id: int) -> int:
 
 def index_encode(type_id: int, blob, off, length, out=None, status=None, stream=None):
     """Index keys of n values (value i = blob[off[i] : off[i] + length[i]]), all
-    HIP tensors; returns a (n, key_size) uint8 tensor."""
+    HIP tensors; returns a (n, key_size) uint8 tensor.  `out`, when given, must
+    start at an 8-byte-aligned address (include/hdxhash.h)."""
     import torch
 
     size = index_key_size(type_id)
@@ -32,6 +33,8 @@ def index_encode(type_id: int, blob, off, length, out=None, status=None, stream=
         assert x.is_cuda and x.is_contiguous()
     if out is None:
         out = torch.empty((n, max(size, 1)), dtype=torch.uint8, device=off.device)
+    assert out.is_cuda and out.is_contiguous() and out.data_ptr() % 8 == 0, \
+        "out must be a contiguous device tensor at an 8-byte-aligned address"
     if stream is None:
         stream = torch.cuda.current_stream(off.device)
     handle = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream

@@ -9,7 +9,7 @@ import ctypes
 
 import numpy as np
 
-from ._lib import check, lib
+from ._lib import HDX_E_BADSIZE, HdxError, check, lib
 
 
 class RegionTable:
@@ -103,12 +103,30 @@ class PointLeaders:
         """Keys packed as a one-attribute batch (blob, key_base[n], key_len[n]
         on the device) -> ((n,) leader vsi, (n,) subspace-0 region position +
         1), int64 on the device; with check, a key no region holds (position
-        0) raises PointLeaderAbort."""
+        0) raises PointLeaderAbort.  A numeric key that is not 0 or 8 bytes
+        long (the reference asserts) raises HdxError(HDX_E_BADSIZE).
+
+        The launch, the status word and the abort check all run on `stream`
+        (default: torch's current stream), and the call returns after `stream`
+        has finished them: no other stream is waited on or synchronised."""
+        import torch
+
         from .hashing import hash_batch_regions
-        ids = hash_batch_regions([key_type], blob, key_base, key_len, [self.leader, self.where], stream=stream)
-        if check:
-            miss = (ids[1] == 0).nonzero()
-            if miss.numel():
-                raise PointLeaderAbort("key %d: no subspace-0 region holds its coordinate "
-                                       "(configuration::point_leader abort()s)" % int(miss[0, 0]))
+        dev = key_base.device
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        elif not isinstance(stream, torch.cuda.Stream):  # a raw hipStream_t handle
+            stream = torch.cuda.ExternalStream(int(stream), device=dev)
+        with torch.cuda.stream(stream):
+            status = torch.zeros(1, dtype=torch.int32, device=dev)
+            ids = hash_batch_regions([key_type], blob, key_base, key_len, [self.leader, self.where],
+                                     status=status, stream=stream)
+            bits = int(status.item())  # waits for `stream` alone
+            if bits & (1 << HDX_E_BADSIZE):
+                raise HdxError(HDX_E_BADSIZE, "a key of type %d is not 0 or 8 bytes long" % key_type)
+            if check:
+                miss = (ids[1] == 0).nonzero()
+                if miss.numel():
+                    raise PointLeaderAbort("key %d: no subspace-0 region holds its coordinate "
+                                           "(configuration::point_leader abort()s)" % int(miss[0, 0]))
         return ids[0], ids[1]

@@ -365,7 +365,10 @@ size_t hdx_index_key_size(uint32_t type);
  *                       little-endian bytes (0.0 when the value is empty).
  * A value whose size is not 0 or 8 gets an all-zero key and sets bit
  * (1 << HDX_E_BADSIZE) in *status_dev (the reference asserts).  Device
- * pointers; asynchronous on `stream`. */
+ * pointers; asynchronous on `stream`.  `out` must be 8-byte aligned (a
+ * uint64_t array works, for FLOAT's 16-byte keys too; 16-byte alignment is
+ * not needed): HDX_E_INVALID otherwise, before any launch.  blob + off[i] may
+ * have any alignment. */
 hdx_status hdx_index_encode_device(uint32_t type, const uint8_t* blob, const uint64_t* off,
                                    const uint32_t* len, uint64_t n, uint8_t* out,
                                    uint32_t* status_dev, hdx_stream stream);
