@@ -764,6 +764,32 @@ HDX_EXPORT uint64_t hdxdbg_region_chunk_objects(uint64_t n, uint32_t attrs_sz) {
     return attrs_sz ? regions_chunk_objects(n, attrs_sz) : 0;
 }
 
+HDX_EXPORT int hdxdbg_wave_geometry(const uint32_t* types, uint32_t attrs_sz, int sweep, uint32_t* out) {
+    BatchArgs a{};
+    std::vector<uint8_t> codes(attrs_sz ? attrs_sz : 1);
+    if (!out || check_schema(types, attrs_sz, codes.data()) != HDX_OK) return -2;
+    WaveGeometry g{};
+    // a forced variant other than the batch product's own (212, which leaves
+    // the sweep's policy alone) may run another form
+    const int forced = hash_variant();
+    if (sweep) {
+        if (attrs_sz > kWsweepMaxAttrs || (forced >= 0 && forced != 212)) return -1;
+        wsweep_product_geometry(attrs_sz, g);
+    } else {
+        std::memcpy(a.codes, codes.data(), std::min(attrs_sz, kKernargCodes));
+        a.A = attrs_sz;
+        a.n = 1;
+        finalize_args(a);
+        if (chosen_variant(a) != 212) return -1;
+        wstage_product_geometry(attrs_sz, g);
+    }
+    if (g.objects == 0) return -1;
+    const uint32_t v[HDXDBG_WAVE_GEOMETRY_WORDS] = {g.objects,  g.window, g.key_region, g.front_pad,
+                                                    g.back_pad, g.passes, g.object_cap};
+    std::memcpy(out, v, sizeof v);
+    return 0;
+}
+
 HDX_EXPORT int hdxdbg_kernel_for(const uint32_t* types, uint32_t attrs_sz, uint64_t n, const char** name) {
     BatchArgs a{};
     std::vector<uint8_t> codes(attrs_sz ? attrs_sz : 1);

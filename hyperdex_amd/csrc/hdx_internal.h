@@ -67,6 +67,14 @@ hipError_t launch_hash_wstage(const BatchArgs& args, hipStream_t stream, int for
 // A <= 128 (else hipErrorInvalidValue).
 hipError_t launch_hash_wstage_product(const BatchArgs& args, hipStream_t stream);
 hipError_t launch_hash_wstage_regions(const BatchArgs& args, hipStream_t stream);  // + args.T tables
+// What a wave of the product's wave-staged forms holds for a schema of A
+// attributes (hdxdbg_wave_geometry, include/hdxhash_debug.h): from the
+// constants their launches use (hdx_wstage.hip, hdx_wsweep.hip).
+struct WaveGeometry {
+    uint32_t objects, window, key_region, front_pad, back_pad, passes, object_cap;
+};
+void wstage_product_geometry(uint32_t A, WaveGeometry& g);
+void wsweep_product_geometry(uint32_t A, WaveGeometry& g);
 // hash + lookup_region (args.T tables in args.t): one fused launch for A <=
 // 128 below kRegionLookupMinObjects, else the hash and one lookup launch per
 // table (hipErrorOutOfMemory when A > 128, coords is NULL and no scratch can

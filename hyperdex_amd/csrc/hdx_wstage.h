@@ -28,8 +28,8 @@
 //   5. one coalesced non-temporal store of the K*A coordinates.
 // A group whose objects are not back to back or do not fit the window is
 // hashed from global memory instead (the A4 loads of hdx_loads.h), so every
-// layout gives the reference's coordinates.  Four waves per workgroup, each
-// with its own window: no workgroup barrier.
+// layout gives the reference's coordinates.  WPB waves per workgroup (the
+// product: one), each with its own window: no workgroup barrier.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -207,6 +207,8 @@ __device__ __forceinline__ Group<NCH> describe_group(const BatchArgs& args, uint
 // window); HT 2 / 3: hash_slot_window's LOOP 2 / 3; HT 5: LOOP 2 with TNUM;
 // HT 6: LOOP 4 with TNUM.
 constexpr uint32_t kFrontHT = 32;
+// bytes kept after the window: dword over-reads past the span's end
+constexpr uint32_t kBackW = 64;
 template <int SHAPE, int HT = 0, int W128 = 0, bool NUM2 = false>
 __device__ __forceinline__ uint64_t hash_slot(const BatchArgs& args, ldsw_t lw, bool staged, uint64_t mybase,
                                               uint32_t s, uint32_t cd, uint64_t d, bool& bad) {
@@ -249,8 +251,8 @@ hash_wstage_kernel(const BatchArgs args) {
     static_assert(NCH >= 1 && NCH <= 4 && WB % 16 == 0, "slot indices are 8 bits; windows whole DMA units");
     static_assert(!(RD && REGIONS), "the fused lookups read the coordinates parked in desc");
     constexpr uint32_t FRONT = HT ? kFrontHT : 0;
-    // +64: dword over-reads past the span; HT: 32 bytes before it (short strings' tail reads)
-    __shared__ __attribute__((aligned(16))) uint8_t win_all[WPB][FRONT + WB + 64];
+    // kBackW: dword over-reads past the span; HT: 32 bytes before it (short strings' tail reads)
+    __shared__ __attribute__((aligned(16))) uint8_t win_all[WPB][FRONT + WB + kBackW];
     __shared__ WStageMeta<NCH, WPB, RD> meta;
     const int lane = threadIdx.x & 63;
     const int w = threadIdx.x >> 6;
@@ -338,8 +340,14 @@ hash_wstage_kernel(const BatchArgs args) {
     if (bad && args.status) atomicOr(args.status, 1u << 2 /* HDX_E_BADSIZE */);
 }
 
-// Launch: K = floor(64 * NCH / A) whole objects per wave (at most 63), four
-// independent waves per 256-thread workgroup, no workgroup barrier.
+// Launch: K = floor(64 * NCH / A) whole objects per wave (at most 63), WPB
+// independent waves per workgroup (the product: one), no workgroup barrier.
+// wstage_objects_per_wave is that K, for the launcher and for the geometry
+// hook (hdx_wstage.hip, wstage_product_geometry).
+// lane o holds object o's base and lane K the next group's first: K <= 63
+inline uint32_t wstage_objects_per_wave(uint32_t passes, uint32_t A, uint32_t cap) {
+    return std::min<uint32_t>(std::min<uint32_t>(64 * passes / A, cap), 63u);
+}
 // The slot plan of BatchArgs::plan for K objects of A attributes.
 inline void fill_wave_plan(BatchArgs& args) {
     for (uint32_t s = 0; s < kWavePlanSlots; ++s) {
@@ -359,8 +367,7 @@ template <int NCH, uint32_t WB, uint32_t KCAP = 63, int SHAPE = 0, int HT = 0, i
           bool REGIONS = false, bool GAP = false, bool ADMA = false, bool PU = true, bool DL = false, int WPB = 4,
           bool XS = false, bool RD = false, bool NT = false, int PRIO = 0, bool PLAN = false, bool NUM2 = false>
 static hipError_t launch_wstage_t(BatchArgs args, hipStream_t stream) {
-    // lane o holds object o's base and lane K the next group's first: K <= 63
-    args.K = std::min<uint32_t>(std::min<uint32_t>((uint32_t)(64 * NCH) / args.A, KCAP), 63u);
+    args.K = wstage_objects_per_wave(NCH, args.A, KCAP);
     if (args.K == 0) return hipErrorInvalidValue;
     static_assert(!PLAN || NCH * 64 <= kWavePlanSlots, "the plan covers two passes");
     if (PLAN) fill_wave_plan(args);

@@ -30,21 +30,47 @@
 
 namespace hdx {
 
+// The product form's geometry: passes of 64 slots per wave, window bytes, the
+// cap on objects per wave, hash_slot's HT (head/tail reads: kFrontHT bytes
+// kept before the window).  The launches below and wstage_product_geometry
+// (hdxdbg_wave_geometry) both read these.
+constexpr int kProductPasses = 2;
+constexpr uint32_t kProductWindow = 8832;
+constexpr uint32_t kProductObjectCap = 63;
+constexpr int kProductHT = 6;
+
+void wstage_product_geometry(uint32_t A, WaveGeometry& g) {
+    g.objects = wstage_objects_per_wave(kProductPasses, A, kProductObjectCap);  // launch_wstage_t's K
+    g.window = kProductWindow;
+    g.key_region = 0;
+    g.front_pad = kProductHT ? kFrontHT : 0;
+    g.back_pad = kBackW;
+    g.passes = kProductPasses;
+    g.object_cap = wstage_objects_per_wave(kProductPasses, 1, kProductObjectCap);
+}
+
+// ORDER 5 / 4 (the class from the table / by selects), REGIONS, then GAP, ADMA, PU on, DL off, one wave
+// per workgroup, XS on, RD off, NT on, PRIO 1; the NUM2 form adds PLAN and NUM2
+template <bool REGIONS>
+static hipError_t launch_product_t(const BatchArgs& args, hipStream_t stream) {
+    constexpr int P = kProductPasses, HT = kProductHT;
+    constexpr uint32_t WB = kProductWindow, CAP = kProductObjectCap;
+    if (num2_schema(args))
+        return launch_wstage_t<P, WB, CAP, 0, HT, 5, 0, REGIONS, true, true, true, false, 1, true, false, true, 1,
+                               true, true>(args, stream);
+    return launch_wstage_t<P, WB, CAP, 0, HT, 4, 0, REGIONS, true, true, true, false, 1, true, false, true, 1>(
+        args, stream);
+}
+
 hipError_t launch_hash_wstage_product(const BatchArgs& args, hipStream_t stream) {
     if (args.n == 0) return hipSuccess;
-    if (num2_schema(args))
-        return launch_wstage_t<2, 8832, 63, 0, 6, 5, 0, false, true, true, true, false, 1, true, false, true, 1, true,
-                               true>(args, stream);
-    return launch_wstage_t<2, 8832, 63, 0, 6, 4, 0, false, true, true, true, false, 1, true, false, true, 1>(args, stream);
+    return launch_product_t<false>(args, stream);
 }
 
 // ... with the fused region lookup (args.T tables; args.coords may be NULL)
 hipError_t launch_hash_wstage_regions(const BatchArgs& args, hipStream_t stream) {
     if (args.n == 0) return hipSuccess;
-    if (num2_schema(args))
-        return launch_wstage_t<2, 8832, 63, 0, 6, 5, 0, true, true, true, true, false, 1, true, false, true, 1, true,
-                               true>(args, stream);
-    return launch_wstage_t<2, 8832, 63, 0, 6, 4, 0, true, true, true, true, false, 1, true, false, true, 1>(args, stream);
+    return launch_product_t<true>(args, stream);
 }
 
 }  // namespace hdx

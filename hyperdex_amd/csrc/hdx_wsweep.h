@@ -53,6 +53,7 @@ typedef uint16_t __attribute__((aligned(1))) u16_u;
 constexpr uint32_t kZero = 0xffffffffu;   // descriptor offset of a slot hashed as 0
 constexpr uint32_t kGlobal = 0x80000000u; // descriptor length bit: hashed from global memory
 constexpr uint32_t kFrontS = 32, kBackS = 64;
+constexpr uint32_t kKeyRegionDiv = 4;     // keys copied apart from the values take at most WB / kKeyRegionDiv bytes
 
 __device__ __forceinline__ uint64_t rl64(uint64_t v, int l) {
     return pack64(__builtin_amdgcn_readlane((uint32_t)v, l), __builtin_amdgcn_readlane((uint32_t)(v >> 32), l));
@@ -148,8 +149,15 @@ __device__ __forceinline__ void copy_span(const uint8_t* src, uint8_t* dst, uint
 
 }  // namespace
 
-// NCH passes of 64 slots; K = min(64 * NCH / A, KCAP) objects per wave; a
-// WB-byte window per wave, four waves per workgroup, no workgroup barrier.
+__host__ __device__ inline uint32_t wsweep_objects_per_wave(uint32_t passes, uint32_t A, uint32_t cap) {
+    const uint32_t k = 64 * passes / A;
+    return k < cap ? k : cap;
+}
+
+// NCH passes of 64 slots; K = min(64 * NCH / A, KCAP) objects per wave
+// (wsweep_objects_per_wave: the kernel, the launcher and the geometry hook,
+// hdx_wsweep.hip); a WB-byte window per wave, WPB waves per workgroup (the
+// product: one), no workgroup barrier.
 // REGIONS (hdx_hash_encoded_regions_device): every object is then looked up
 // in the a.T region tables (configuration::lookup_region, hdx_region_lookup.h:
 // the interval index, or the scan), lane = object, from the coordinates
@@ -188,7 +196,7 @@ hash_sweep_wstage_kernel(const EncodedArgs a) {
     uint32_t* cnt = cnt_all[w];
     uint8_t* codes = codes_all[w];
     const uint32_t A = a.A;
-    const uint32_t K = std::min<uint32_t>(SL / A, KCAP);
+    const uint32_t K = wsweep_objects_per_wave(NCH, A, KCAP);
     const uint64_t o0 = ((uint64_t)(XS ? xcd_block() : blockIdx.x) * WPB + w) * K;
     if (o0 >= a.n) return;
     const uint32_t nobj = (uint32_t)std::min<uint64_t>(K, a.n - o0);
@@ -245,7 +253,7 @@ hash_sweep_wstage_kernel(const EncodedArgs a) {
     } else {
         if (kruns) {
             const uint64_t kend = rl64(koff + klen, (int)nobj - 1);
-            kspan = kend - k0 + klead <= WB / 4;
+            kspan = kend - k0 + klead <= WB / kKeyRegionDiv;
             keys_in = kspan;
             if (kspan) {
                 kreg = (klead + (uint32_t)(kend - k0) + 15) & ~15u;
@@ -258,7 +266,7 @@ hash_sweep_wstage_kernel(const EncodedArgs a) {
         const uint32_t ku = (uint32_t)lane < nobj ? ((uint32_t)(kaddr & 15) + klen + 15) >> 4 : 0u;
         if (!kspan && KUNITS) {
             for (uint32_t o = 0; o < nobj; ++o) kU = std::max(kU, (uint32_t)__builtin_amdgcn_readlane(ku, (int)o));
-            if (kU && nobj * kU <= 64 && 16 * nobj * kU <= WB / 4) {
+            if (kU && nobj * kU <= 64 && 16 * nobj * kU <= WB / kKeyRegionDiv) {
                 const uint32_t magic = (65536u + kU - 1) / kU;  // lane / kU for lane < 64, kU <= 64
                 const uint32_t o = ((uint32_t)lane * magic) >> 16, k = (uint32_t)lane - o * kU;
                 const uint64_t src = sh64(kaddr & ~15ull, (int)(o & 63)) + 16ull * k;
@@ -277,7 +285,7 @@ hash_sweep_wstage_kernel(const EncodedArgs a) {
                 (uint32_t)lane < nobj ? ((uint32_t)((uintptr_t)(a.keys + koff) & 3) + klen + 3) >> 2 : 0u;
             kdx = wave_scan_dpp(kdw) - kdw;
             const uint32_t td = __builtin_amdgcn_readlane(kdx + kdw, 63);
-            keys_in = 4 * td <= WB / 4;
+            keys_in = 4 * td <= WB / kKeyRegionDiv;
             kreg = keys_in ? (4 * td + 15) & ~15u : 0u;  // the values' region starts 16-byte aligned
             if (keys_in) {
                 for (uint32_t u0 = 0; u0 < td; u0 += 64) {
@@ -453,7 +461,7 @@ template <int NCH, uint32_t WB, uint32_t KCAP, bool REGIONS = false, bool GAP = 
           bool ASM = false, bool PU = true, bool BF = false, bool RECS = true, bool KUNITS = true, bool DL = false,
           int WPB = 4, bool XS = false, int PRIO = 0, bool NUM2 = false>
 static hipError_t launch_wsweep_t(const EncodedArgs& a, hipStream_t stream) {
-    const uint32_t K = std::min<uint32_t>(64 * NCH / a.A, KCAP);
+    const uint32_t K = wsweep_objects_per_wave(NCH, a.A, KCAP);
     if (K == 0) return hipErrorInvalidValue;
     if (NUM2 && !num2_codes(a)) return hipErrorInvalidValue;
     const uint64_t waves = (a.n + K - 1) / K;

@@ -33,11 +33,30 @@ namespace hdx {
 // read per slot in a pass holding long and short strings): 3.247 vs 3.266 and
 // 3.261 vs 3.287 ms per 10 M on the key column (debug 298 = LOOP 13,
 // profiles/r6/ab_loop4.jsonl).
+// The product form's geometry: passes of 64 slots per wave, window bytes, the
+// cap on objects per wave.  The launch below and wsweep_product_geometry
+// (hdxdbg_wave_geometry) both read these.
+constexpr int kProductPasses = 2;
+constexpr uint32_t kProductWindow = 9728;
+constexpr uint32_t kProductObjectCap = 7;
+
+void wsweep_product_geometry(uint32_t A, WaveGeometry& g) {
+    g.objects = wsweep_objects_per_wave(kProductPasses, A, kProductObjectCap);  // the kernel's and the launcher's K
+    g.window = kProductWindow;
+    g.key_region = kProductWindow / kKeyRegionDiv;
+    g.front_pad = kFrontS;
+    g.back_pad = kBackS;
+    g.passes = kProductPasses;
+    g.object_cap = kProductObjectCap;
+}
+
 template <bool REG, bool RECS>
 static hipError_t launch_wsweep_product_t(const EncodedArgs& a, hipStream_t stream) {
+    constexpr int P = kProductPasses;
+    constexpr uint32_t WB = kProductWindow, CAP = kProductObjectCap;
     if (num2_codes(a))
-        return launch_wsweep_t<2, 9728, 7, REG, true, 0, 14, false, true, true, RECS, true, false, 1, true, 4, true>(a, stream);
-    return launch_wsweep_t<2, 9728, 7, REG, true, 0, 14, false, true, true, RECS, true, false, 1, true, 4>(a, stream);
+        return launch_wsweep_t<P, WB, CAP, REG, true, 0, 14, false, true, true, RECS, true, false, 1, true, 4, true>(a, stream);
+    return launch_wsweep_t<P, WB, CAP, REG, true, 0, 14, false, true, true, RECS, true, false, 1, true, 4>(a, stream);
 }
 
 hipError_t launch_hash_wsweep_product(const EncodedArgs& a, hipStream_t stream) {

@@ -325,6 +325,21 @@ def kernel_for(types, n: int):
     return v, (name.value or b"").decode()
 
 
+WAVE_GEOMETRY_FIELDS = ("objects", "window", "key_region", "front_pad", "back_pad", "passes", "object_cap")
+
+
+def wave_geometry(types, sweep: bool = False):
+    """hdxdbg_wave_geometry: what one wave of the wave-staged batch kernel
+    (sweep=False) or stored-object sweep (sweep=True) holds for this schema, as
+    a dict of WAVE_GEOMETRY_FIELDS; None when the schema takes another form."""
+    t = _u32_array(types)
+    out = np.zeros(len(WAVE_GEOMETRY_FIELDS), dtype=np.uint32)
+    r = lib().hdxdbg_wave_geometry(t.ctypes.data, len(t), 1 if sweep else 0, out.ctypes.data)
+    if r == -2:
+        raise HdxError(_lib.HDX_E_INVALID, "wave_geometry: bad schema")
+    return None if r != 0 else dict(zip(WAVE_GEOMETRY_FIELDS, (int(x) for x in out)))
+
+
 # ---- the device set (hdx_init_mask; include/hdxhash.h "multi-device") ------
 
 def init_mask(mask: int) -> None:

@@ -3,8 +3,9 @@
  * boundary).
  *
  * Both libraries: hdxdbg_kernel_for (which kernel the automatic policy runs),
- * hdxdbg_stream_probe (bench.py's practical HBM ceiling) and
- * hdxdbg_region_chunk_objects (tests/test_scale.py's chunk edges).
+ * hdxdbg_stream_probe (bench.py's practical HBM ceiling),
+ * hdxdbg_region_chunk_objects (tests/test_scale.py's chunk edges) and
+ * hdxdbg_wave_geometry (tests/test_window_edges.py's window boundaries).
  * libhdxhash_dbg.so only (HDX_DEBUG_BUILD, hyperdex_amd/csrc/Makefile):
  * hdxdbg_set_kernel_variant / hdxdbg_kernel_variant, used by
  * scripts/ab_variants.py and the variant parity tests.  The product library
@@ -42,6 +43,26 @@ int hdxdbg_init_devices(const int* devices, int n);
 /* Objects per scratch chunk of the regions entry points when the caller
  * wants no coordinates (n objects of attrs_sz attributes; hdx_regions.hip). */
 uint64_t hdxdbg_region_chunk_objects(uint64_t n, uint32_t attrs_sz);
+/* What one wave of the wave-staged form holds for this schema: sweep == 0 the
+ * batch kernel hdx_hash_batch_device launches (hdx_wstage.hip; under the
+ * current selection, when that is the product's form), sweep != 0 the
+ * stored-object sweep of hdx_hash_encoded_device (hdx_wsweep.hip).  Fills
+ * out[HDXDBG_WAVE_GEOMETRY_WORDS]: objects per wave K; window bytes WB; the
+ * bytes of the window that keys copied apart from their values may take (0
+ * for the batch kernel); the bytes kept readable before and after the window
+ * (hash_slot_window's reads around a short string); passes of 64 slots per
+ * wave NCH and the cap on K, so that K = min(64 * NCH / attrs_sz, cap).
+ * tests/test_window_edges.py builds its boundary cases from these.  Returns
+ * 0, -2 on a bad schema, -1 when the schema takes another form.
+ * It answers for the product's two forms only.  In the debug library, with a
+ * variant selected: 212 (the batch product's own id, which leaves the sweep's
+ * policy alone) answers as the automatic policy does, for any schema of up to
+ * 128 attributes; every other selection returns -1 for both kernels, the
+ * other wave-staged A/B variants (213..216, 258, 273, ...: windows and
+ * object counts of their own) and the ones that would leave the sweep alone
+ * included. */
+#define HDXDBG_WAVE_GEOMETRY_WORDS 7
+int hdxdbg_wave_geometry(const uint32_t* types, uint32_t attrs_sz, int sweep, uint32_t* out);
 
 #ifdef __cplusplus
 }
