@@ -12,6 +12,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
 _REF = None
+_REF_HASH = None
 
 
 def build():
@@ -71,6 +72,69 @@ def ref_lib():
         R.ref_ordered_encode_double.restype = ctypes.c_uint64
         _REF = R
     return _REF
+
+
+def ref_hash_lib():
+    """oracle/_ref/libref_hash.so (the reference's hash.cc, datatype_*.cc,
+    ordered_encoding.cc and city.cc behind ref_hash_glue.cc), or None."""
+    global _REF_HASH
+    if _REF_HASH is None:
+        path = os.path.join(_HERE, "_ref", "libref_hash.so")
+        if not os.path.exists(path):
+            return None
+        R = ctypes.CDLL(path)
+        u64, u32, vp = ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p
+        R.ref_hash.argtypes = [u32, vp, ctypes.c_size_t, ctypes.POINTER(u64)]
+        R.ref_hash.restype = ctypes.c_int
+        R.ref_hash_batch.argtypes = [u32, vp, vp, vp, u64, vp]
+        R.ref_hash_batch.restype = ctypes.c_int
+        R.ref_hash_object.argtypes = [vp, u32, vp, vp, vp, u64, vp]
+        R.ref_hash_object.restype = ctypes.c_int
+        _REF_HASH = R
+    return _REF_HASH
+
+
+def ref_hash(type_id: int, data: bytes):
+    """The reference's hash(hyperdatatype, slice) -> (u64, err); err 1: not one
+    of the nine hashable types, 2: a numeric neither empty nor 8 bytes (the
+    reference asserts on both, so the glue refuses them)."""
+    buf = ctypes.create_string_buffer(bytes(data), max(len(data), 1))
+    out = ctypes.c_uint64(0)
+    err = ref_hash_lib().ref_hash(type_id, buf, len(data), ctypes.byref(out))
+    return out.value, err
+
+
+def ref_hash_values(type_id: int, blob, off, lens):
+    """The reference's hash(type_id, blob[off[i]:off[i] + lens[i]]) for every i
+    (values are read in place: blob's own alignment counts) -> (u64 array, err)."""
+    blob = np.ascontiguousarray(blob, dtype=np.uint8)
+    off = np.ascontiguousarray(off, dtype=np.uint64)
+    lens = np.ascontiguousarray(lens, dtype=np.uint32)
+    assert off.shape == lens.shape
+    assert off.size == 0 or int((off + lens.astype(np.uint64)).max()) <= blob.size
+    out = np.zeros(off.size, dtype=np.uint64)
+    if blob.size == 0:
+        blob = np.zeros(1, dtype=np.uint8)
+    err = ref_hash_lib().ref_hash_batch(type_id, blob.ctypes.data, off.ctypes.data, lens.ctypes.data, off.size,
+                                        out.ctypes.data)
+    return out, err
+
+
+def ref_hash_objects(types, blob, obj_base, attr_len):
+    """The reference's hash(schema, key, value, hs) over the packed layout of
+    hash_batch (a schema of the nine hashable types only) -> (coords (n, A), err)."""
+    types = np.ascontiguousarray(types, dtype=np.uint32)
+    blob = np.ascontiguousarray(blob, dtype=np.uint8)
+    obj_base = np.ascontiguousarray(obj_base, dtype=np.uint64)
+    attr_len = np.ascontiguousarray(attr_len, dtype=np.uint32)
+    A, n = len(types), len(obj_base)
+    assert attr_len.size == n * A
+    coords = np.zeros(n * A, dtype=np.uint64)
+    if blob.size == 0:
+        blob = np.zeros(1, dtype=np.uint8)
+    err = ref_hash_lib().ref_hash_object(types.ctypes.data, A, blob.ctypes.data, obj_base.ctypes.data,
+                                         attr_len.ctypes.data, n, coords.ctypes.data)
+    return coords.reshape(n, A), err
 
 
 def cityhash64(data: bytes) -> int:

@@ -9,6 +9,9 @@
 //   dropin_test            check the reference values
 //   dropin_test bench N    also time N config-3b-shaped objects through
 //                          hash(schema, key, value, hs); prints ns/object
+//   dropin_test values F   hash every record of file F ([u32 type][u32 len]
+//                          [len bytes], little-endian) through
+//                          hash(hyperdatatype, e::slice); one hex value per line
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -94,8 +97,27 @@ static int bench(long n) {
     return 0;
 }
 
+static int values(const char* path) {
+    FILE* f = fopen(path, "rb");
+    if (!f) return 2;
+    std::vector<uint8_t> buf;
+    uint32_t head[2];
+    while (fread(head, sizeof head[0], 2, f) == 2) {
+        buf.resize(head[1] ? head[1] : 1);
+        if (head[1] && fread(&buf[0], 1, head[1], f) != head[1]) {
+            fclose(f);
+            return 2;
+        }
+        const uint64_t h = hyperdex::hash(static_cast<hyperdatatype>(head[0]), e::slice(&buf[0], head[1]));
+        printf("%016llx\n", (unsigned long long)h);
+    }
+    fclose(f);
+    return 0;
+}
+
 int main(int argc, char** argv) {
     using hyperdex::hash;
+    if (argc > 2 && strcmp(argv[1], "values") == 0) return values(argv[2]);
     const char* key = "hello world, this is a 64 byte key padded out to the full length";
     int64_t i42 = 42;
     double f35 = 3.5;
