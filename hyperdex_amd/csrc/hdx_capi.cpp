@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "hdx_host.h"
+#include "hdx_variants.h"
 #include "../../include/hdxhash_debug.h"
 
 #ifndef HDX_DEBUG_BUILD
@@ -752,6 +753,7 @@ HDX_EXPORT hdx_status hdx_lookup_region_device(hdx_region_table t, const uint64_
 #if HDX_DEBUG_BUILD
 HDX_EXPORT int hdxdbg_set_kernel_variant(int variant) { return set_hash_variant(variant); }
 HDX_EXPORT int hdxdbg_kernel_variant(void) { return hash_variant(); }
+HDX_EXPORT int hdxdbg_variant_entries(int variant) { return variant_entries(variant); }
 #endif
 
 HDX_EXPORT int hdxdbg_stream_probe(const void* src, uint64_t bytes, uint64_t* sink, int write, void* stream) {

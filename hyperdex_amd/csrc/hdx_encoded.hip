@@ -26,6 +26,7 @@
 #include "hdx_internal.h"
 #include "hdx_loads.h"
 #include "hdx_region_lookup.h"
+#include "hdx_variants.h"
 
 namespace hdx {
 
@@ -364,6 +365,26 @@ static hipError_t launch_encoded(const EncodedArgs& a_in, hipStream_t stream) {
     return hipGetLastError();
 }
 
+#if HDX_DEBUG_BUILD
+// Debug library: the gather sweep's rows of the stored-object sweep's variant
+// table (hdx_variants.h; the wave-staged forms' rows are in hdx_wsweep_dbg.hip).
+static const SweepRow kGatherRows[] = {
+    {33, launch_encoded<true, false>, "43 with the phase-0 line touch (measured 11 % slower, r1u)"},
+    {43, launch_encoded<false, false>, "byte-addressed loads, 64 objects per wave"},
+    {47, launch_encoded<false, true, 0, 64>, "49 with 64 objects per wave"},
+    {48, launch_encoded<false, true, 0, 16>, "49 with 16 objects per wave"},
+    {49, launch_encoded<false, true, 0, 32>, "the gather sweep (the product's sweep up to round 2)"},
+    {57, launch_encoded<false, true, 1>, "debug shape: the walk alone (WRONG coordinates)"},
+    {58, launch_encoded<false, true, 2>, "debug shape: phase 2 loads only (WRONG coordinates)"},
+    {170, launch_encoded<false, true, 0, 32, false, true>, "49 with the numeric walk (non-string values hashed during the walk)"},
+    {171, launch_encoded<false, true, 0, 64, false, true>, "170 with 64 objects per wave"},
+    {172, launch_encoded<false, true, 0, 16, false, true>, "170 with 16 objects per wave"},
+    {173, launch_encoded<false, true, 0, 32, false, true, true>, "170 with runs of fixed-size values read in one round trip"},
+    {174, launch_encoded<false, true, 0, 64, false, true, true>, "173 with 64 objects per wave"},
+};
+VariantRows<EncodedArgs> gather_sweep_variant_rows() { return kGatherRows; }
+#endif
+
 hipError_t launch_hash_encoded(const EncodedArgs& a_in, hipStream_t stream) {
     if (a_in.n == 0) return hipSuccess;
     EncodedArgs a = a_in;
@@ -388,11 +409,9 @@ hipError_t launch_hash_encoded(const EncodedArgs& a_in, hipStream_t stream) {
         return no_scratch ? hipErrorOutOfMemory : e;
     }
     a.a_magic = (uint32_t)(((1ull << 31) + a.A - 1) / a.A);
-    // default: dword-aligned loads (5.49 vs 6.14 ms per 10 M config-3b objects,
-    // profiles/r1/ab_a4_cfg5.jsonl), 32 objects per wave (5.05 vs 5.31 ms for
-    // 64 (variant 47) and 5.88 for 16 (48), ab_cfg5_objects_per_wave.jsonl);
-    // variant 43 = byte-addressed loads, 64 objects per wave, variant 33 adds
-    // the phase-0 line touch to those (measured 11 % slower, r1u).
+    // the gather sweep: dword-aligned loads (5.49 vs 6.14 ms per 10 M config-3b
+    // objects, profiles/r1/ab_a4_cfg5.jsonl), 32 objects per wave (5.05 vs 5.31 ms
+    // for 64 (variant 47) and 5.88 for 16 (48), ab_cfg5_objects_per_wave.jsonl).
     // Retired (profiles/r1/ab_cfg5_*.jsonl): class-sorted passes over the whole
     // wave or over groups of 2 / 4 passes, 16 / 32 objects per wave, and a
     // lane-per-object walk-and-hash kernel — all slower
@@ -447,65 +466,12 @@ hipError_t launch_hash_encoded(const EncodedArgs& a_in, hipStream_t stream) {
         return launch_encoded<false, true, 0, 32, true>(a, stream);
     }
 #if HDX_DEBUG_BUILD
-    switch (hash_variant()) {
-        case 43: return launch_encoded<false, false>(a, stream);
-        case 33: return launch_encoded<true, false>(a, stream);
-        case 57: return launch_encoded<false, true, 1>(a, stream);  // debug shape: the walk alone (WRONG coords)
-        case 58: return launch_encoded<false, true, 2>(a, stream);  // debug shape: phase 2 loads only (WRONG coords)
-        case 47: return launch_encoded<false, true, 0, 64>(a, stream);
-        // numeric walk (non-string value attributes hashed during the walk): 32 / 64 objects per wave
-        case 170: return launch_encoded<false, true, 0, 32, false, true>(a, stream);
-        case 171: return launch_encoded<false, true, 0, 64, false, true>(a, stream);
-        case 172: return launch_encoded<false, true, 0, 16, false, true>(a, stream);
-        // ... plus runs of fixed-size values read in one round trip: 32 / 64 objects per wave
-        case 173: return launch_encoded<false, true, 0, 32, false, true, true>(a, stream);
-        case 174: return launch_encoded<false, true, 0, 64, false, true, true>(a, stream);
-        case 48: return launch_encoded<false, true, 0, 16>(a, stream);
-        // wave-staged (hdx_wsweep_dbg.hip): 230 6 objects / 2 passes, 231 7 objects, 232 11 objects / 3 passes,
-        // 236 = 230 without the pass-boundary gap, 237 / 238 its debug shapes (no hash / no hash, no walk),
-        // 239 = 230 with the one-block > 64-byte loop, 242 without the shared final mix16,
-        // 243 with the DMA as inline asm, 244 with the pass loop not unrolled, 245 with the
-        // branchy class, 246 without TNUM
-        case 230: case 231: case 232: case 236: case 237: case 238: case 239: case 242: case 243: case 244: case 245: case 246: {
-            const hipError_t e = launch_hash_wsweep(a, stream, hash_variant() - 230);
-            if (e != hipErrorInvalidValue) return e;
-            break;
-        }
-        case 256: case 257: case 258: case 259: case 270: case 271: case 272: case 273: {  // the product sweep with one / two waves per
-            // workgroup, 7.75 KiB windows, four waves; 270: XCD-aware block order; 271: 7 objects per wave
-            const int v = hash_variant();
-            const hipError_t e = launch_hash_wsweep(a, stream, v == 270 ? 27 : v == 271 ? 28 : v == 272 ? 29 : v == 273 ? 30
-                                                                                                     : v - 256 + 23);
-            if (e != hipErrorInvalidValue) return e;
-            break;
-        }
-        case 277: {  // the product sweep without wave priorities
-            const hipError_t e = launch_hash_wsweep(a, stream, 31);
-            if (e != hipErrorInvalidValue) return e;
-            break;
-        }
-        case 313: case 314: case 315: {  // the product sweep's debug shapes: no hash / no hash, no walk / no copy, no walk
-            const hipError_t e = launch_hash_wsweep(a, stream, hash_variant() - 313 + 38);
-            if (e != hipErrorInvalidValue) return e;
-            break;
-        }
-        case 298: {  // the product sweep before LOOP 4 (LOOP 13: two head reads per divergent pass)
-            const hipError_t e = launch_hash_wsweep(a, stream, 37);
-            if (e != hipErrorInvalidValue) return e;
-            break;
-        }
-        case 250: case 251: case 252: case 253: case 254: case 255: {  // the product sweep without the record
-            // span; 251 also with round 3's dword key gather; 252 its debug shape: no copy, no walk, the hash on
-            // made-up descriptors; 253 / 254 the product's non-record / record forms with round 3's per-KiB span
-            // copy; 255 the non-record form with round 3's walk reads (dword pairs + v_alignbyte)
-            const hipError_t e = launch_hash_wsweep(a, stream, hash_variant() - 250 + 17);
-            if (e != hipErrorInvalidValue) return e;
-            break;
-        }
-        default: break;
+    // a forced form of the sweep's table; hipErrorInvalidValue (a schema the
+    // form does not take, no coordinates wanted) leaves it to the product
+    if (const SweepRow* forced = sweep_variant(hash_variant())) {
+        const hipError_t e = forced->launch(a, stream);
+        if (e != hipErrorInvalidValue) return e;
     }
-    // 49: the gather sweep (the product's sweep up to round 2), for A/B runs
-    if (hash_variant() == 49) return launch_encoded<false, true, 0, 32>(a, stream);
 #endif
     // the wave-staged sweep (hdx_wsweep.h): 4.65 vs 5.10 ms per 10 M
     // config-3b objects, 24.2 vs 25.1 ms at 50 M (profiles/r3/ab_wsweep.jsonl)

@@ -61,10 +61,8 @@ struct BatchArgs {
 
 hipError_t launch_hash_batch(const BatchArgs& args, hipStream_t stream);
 // Wave-staged hash (hdx_wstage.hip): K whole objects per wave copied into an
-// LDS window by DMA and hashed from LDS; form = passes / window size.
-hipError_t launch_hash_wstage(const BatchArgs& args, hipStream_t stream, int form);  // debug library
-// Its product form (hdx_wstage.hip): two passes per wave, head/tail hashing;
-// A <= 128 (else hipErrorInvalidValue).
+// LDS window by DMA and hashed from LDS.  The product form: two passes per
+// wave, head/tail hashing; A <= 128 (else hipErrorInvalidValue).
 hipError_t launch_hash_wstage_product(const BatchArgs& args, hipStream_t stream);
 hipError_t launch_hash_wstage_regions(const BatchArgs& args, hipStream_t stream);  // + args.T tables
 // What a wave of the product's wave-staged forms holds for a schema of A
@@ -86,21 +84,16 @@ hipError_t launch_hash_batch_regions(const BatchArgs& args, hipStream_t stream);
 hipError_t launch_hash_wide(const BatchArgs& args, hipStream_t stream);
 struct EncodedArgs;
 hipError_t launch_hash_sweep_wide(const EncodedArgs& a, hipStream_t stream);
-// Debug library only (hdx_wide_dbg.hip): the wide sweep's retired forms.
-hipError_t launch_sweep_wide_debug(const EncodedArgs& a, hipStream_t stream, int variant);
 // Fills args.uniform_code from args.codes[0..A), and inv_A / a_magic from A.
 void finalize_args(BatchArgs& args);
-// Kernel variants (hdx_kernels.hip, variant_kernel_name): the automatic policy's
-// choices and the alternatives scripts/ab_variants.py times against them.
+// The automatic policy's kernels by variant id (hdx_kernels.hip,
+// variant_kernel_name); any other id is hipErrorInvalidValue.
 hipError_t launch_hash_batch_variant(const BatchArgs& args, hipStream_t stream, int variant);
-// The variant launch_hash_batch uses: -1 (the automatic policy) in the product
-// library; libhdxhash_dbg.so (HDX_DEBUG_BUILD) adds a process-wide selection.
+// The forced variant: -1 (the automatic policy) in the product library;
+// libhdxhash_dbg.so (HDX_DEBUG_BUILD) adds a process-wide selection, looked up
+// in each entry point's variant table (hdx_variants.h).
 int hash_variant();
 int set_hash_variant(int v);  // debug build only: -2 if unknown, else the previous selection
-// Debug library only (hdx_kernels_dbg.hip): the retired A/B forms of the batch
-// hash and of the fused hash + lookup.
-hipError_t launch_debug_variant(const BatchArgs& args, hipStream_t stream, int variant);
-hipError_t launch_fused_debug(const BatchArgs& args, hipStream_t stream, int variant);
 // The variant launch_hash_batch would run for args, and its kernel's symbol.
 int chosen_variant(const BatchArgs& args);
 const char* variant_kernel_name(int v);
@@ -208,11 +201,9 @@ hipError_t launch_copy_linear(const void* const* src, void* const* dst, const ui
                               hipStream_t stream);
 // The wave-staged sweep (hdx_wsweep.h): K objects per wave, keys and values
 // copied into LDS by DMA, the walk and the hashing from LDS; coords != NULL,
-// A <= 64 * passes (else hipErrorInvalidValue).  The product form, and (debug
-// library) its A/B forms.
+// A <= 64 * passes (else hipErrorInvalidValue).  The product form.
 constexpr uint32_t kWsweepMaxAttrs = 128;
 hipError_t launch_hash_wsweep_product(const EncodedArgs& a, hipStream_t stream);
-hipError_t launch_hash_wsweep(const EncodedArgs& a, hipStream_t stream, int form);
 // HBM streaming probe (hdx_synth.hip): read `bytes` (write = 1: plus one
 // 8-byte store per 64 bytes read into sink[bytes / 64]).
 hipError_t launch_stream_probe(const uint8_t* src, uint64_t bytes, uint64_t* sink, int write, hipStream_t s);

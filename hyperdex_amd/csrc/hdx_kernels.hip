@@ -10,19 +10,19 @@
 //                         LDS, optionally counting-sorted by work class so a
 //                         wave's lanes run the same CityHash regime.
 // launch_hash_batch picks one per schema and size (auto_variant).  Variant ids
-// are those of the round-1 A/B logs (profiles/r1/ab_*.jsonl); the ids of
-// retired experiments (0-11, 13-17, 22-24, 27-29, 32-34, 36, 38, 39, 44-46,
-// 50-53, 59: rounds-per-wave kernels, non-temporal loads, workgroup-barrier
-// sorts, LDS-staged blocks, larger sort windows, occupancy caps, workgroup LDS
-// windows with and without pipelining) are no longer built; their results are
-// in DESIGN.md §4 and the logs.
-// The kernel bodies and launch templates are in hdx_regroup.h; the retired
-// experiments (debug library only) in hdx_kernels_dbg.hip.
+// are those of the A/B logs (profiles/r*/ab_*.jsonl); ids that are in no
+// variant table (hdx_variants.h) belong to retired experiments, whose results
+// are in DESIGN.md §4 and the logs.
+// The kernel bodies and launch templates are in hdx_regroup.h.  The debug
+// library looks a forced id up in the entry point's variant table (the
+// alternatives' rows are in hdx_kernels_dbg.hip and hdx_wstage_dbg.hip); the
+// product library has only the policy's switch.
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
 
 #include "hdx_regroup.h"
+#include "hdx_variants.h"
 
 #ifndef HDX_DEBUG_BUILD
 #define HDX_DEBUG_BUILD 0
@@ -43,12 +43,7 @@ hipError_t launch_hash_batch_variant(const BatchArgs& args, hipStream_t stream, 
         case 46: return launch_regroup<8, true, true, true, false, false, true, 1, 1>(args, stream);
         case 212: return launch_hash_wstage_product(args, stream);  // hdx_wstage.hip
         case 300: return launch_hash_wide(args, stream);            // hdx_wide.hip
-        default:
-#if HDX_DEBUG_BUILD
-            return launch_debug_variant(args, stream, variant);  // hdx_kernels_dbg.hip
-#else
-            return hipErrorInvalidValue;
-#endif
+        default: return hipErrorInvalidValue;
     }
 }
 
@@ -83,9 +78,7 @@ hipError_t launch_hash_batch_regions(const BatchArgs& args, hipStream_t stream) 
         return no_scratch ? hipErrorOutOfMemory : e;
     }
 #if HDX_DEBUG_BUILD
-    const int v = hash_variant();
-    if (v >= 100 && v < 120) return launch_fused_debug(args, stream, v);  // hdx_kernels_dbg.hip
-    if (v == 217) return launch_hash_wstage_regions(args, stream);
+    if (const BatchRow* forced = batch_regions_variant(hash_variant())) return forced->launch(args, stream);
 #endif
     switch (auto_variant(args)) {
         case 25: case 20: return launch_regroup_regions<8, false, false, false, 0, true>(args, stream);
@@ -177,8 +170,13 @@ void finalize_args(BatchArgs& args) {
 }
 
 hipError_t launch_hash_batch(const BatchArgs& args, hipStream_t stream) {
-    const int v = hash_variant();
-    return launch_hash_batch_variant(args, stream, v < 0 ? auto_variant(args) : v);
+#if HDX_DEBUG_BUILD
+    if (const int v = hash_variant(); v >= 0) {  // forced: its row of the batch table, or an error
+        const BatchRow* forced = batch_variant(v);
+        return forced ? forced->launch(args, stream) : hipErrorInvalidValue;
+    }
+#endif
+    return launch_hash_batch_variant(args, stream, auto_variant(args));
 }
 
 int chosen_variant(const BatchArgs& args) {

@@ -29,6 +29,7 @@
 #include <stdint.h>
 
 #include "hdx_regroup.h"
+#include "hdx_variants.h"
 #include "hdx_wide.h"
 
 #ifndef HDX_DEBUG_BUILD
@@ -240,18 +241,22 @@ static hipError_t launch_sweep_wide_two(const EncodedArgs& a, hipStream_t stream
     return hipGetLastError();
 }
 
+#if HDX_DEBUG_BUILD
+// Debug library: the two-launch forms' rows of the wide sweep's variant table
+// (hdx_variants.h; the other forms' rows are in hdx_wide_dbg.hip).
+static const SweepRow kTwoLaunchRows[] = {
+    {309, launch_sweep_wide_two<1>, "the walk storing its descriptors one per step group"},
+    {310, launch_sweep_wide_two<8>, "the walk storing its descriptors 8 per step group"},
+    {311, launch_sweep_wide_two<16, true>, "the hash class-sorted per 256 attributes"},
+};
+VariantRows<EncodedArgs> wide_two_variant_rows() { return kTwoLaunchRows; }
+#endif
+
 hipError_t launch_hash_sweep_wide(const EncodedArgs& a, hipStream_t stream) {
     if (a.n == 0) return hipSuccess;
     if (!a.codes_dev || !a.coords) return hipErrorInvalidValue;
 #if HDX_DEBUG_BUILD
-    switch (hash_variant()) {
-        case 304: case 305: case 306: case 307: case 308: case 312:  // hdx_wide_dbg.hip
-            return launch_sweep_wide_debug(a, stream, hash_variant());
-        case 309: return launch_sweep_wide_two<1>(a, stream);  // the walk's stores one per step
-        case 310: return launch_sweep_wide_two<8>(a, stream);  // ... 8 at a time
-        case 311: return launch_sweep_wide_two<16, true>(a, stream);  // the hash class-sorted per 256 attributes
-        default: break;
-    }
+    if (const SweepRow* forced = wide_sweep_variant(hash_variant())) return forced->launch(a, stream);
 #endif
     return launch_sweep_wide_two<16>(a, stream);
 }

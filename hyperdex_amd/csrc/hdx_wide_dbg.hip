@@ -1,5 +1,6 @@
 // hdx_wide_dbg.hip — debug forms of the wide sweep (libhdxhash_dbg.so only;
-// hdxdbg_set_kernel_variant 304-308, 312): measured against the product's two
+// hdxdbg_set_kernel_variant 304-308, 312) and their rows of the wide sweep's
+// variant table (hdx_variants.h): measured against the product's two
 // launches (hdx_wide.hip) and kept for the A/B record (DESIGN §4.7,
 // profiles/r6/ab_wide_stream.jsonl, ab_wide_fused.jsonl).
 #include <hip/hip_runtime.h>
@@ -7,6 +8,7 @@
 #include <algorithm>
 #include <stdint.h>
 
+#include "hdx_variants.h"
 #include "hdx_wide.h"
 
 namespace hdx {
@@ -220,16 +222,14 @@ static hipError_t launch_sweep_wide_stream(const EncodedArgs& a, hipStream_t str
     return hipGetLastError();
 }
 
-hipError_t launch_sweep_wide_debug(const EncodedArgs& a, hipStream_t stream, int variant) {
-    switch (variant) {
-        case 304: return launch_sweep_wide_stream<4096>(a, stream);
-        case 305: return launch_sweep_wide_stream<2048>(a, stream);
-        case 306: return launch_sweep_wide_stream<8192>(a, stream);
-        case 307: return launch_sweep_wide_stream<4096, 1>(a, stream);  // debug shape: no hash
-        case 308: return launch_sweep_wide_stream<4096, 2>(a, stream);  // debug shape: no walk
-        case 312: return launch_sweep_wide_fused(a, stream);              // one launch, a lane per object
-        default: return hipErrorInvalidValue;
-    }
-}
+static const SweepRow kRows[] = {
+    {304, launch_sweep_wide_stream<4096>, "streamed through an LDS ring in 4 KiB chunks"},
+    {305, launch_sweep_wide_stream<2048>, "304 with 2 KiB chunks"},
+    {306, launch_sweep_wide_stream<8192>, "304 with 8 KiB chunks"},
+    {307, launch_sweep_wide_stream<4096, 1>, "debug shape of 304: no hash (WRONG coordinates)"},
+    {308, launch_sweep_wide_stream<4096, 2>, "debug shape of 304: no walk (WRONG coordinates)"},
+    {312, launch_sweep_wide_fused, "one launch, a lane per object (walk and hash fused)"},
+};
+VariantRows<EncodedArgs> wide_sweep_variant_rows() { return kRows; }
 
 }  // namespace hdx

@@ -363,22 +363,41 @@ inline bool num2_schema(const BatchArgs& args) {
     return args.A <= kKernargCodes;
 }
 
-template <int NCH, uint32_t WB, uint32_t KCAP = 63, int SHAPE = 0, int HT = 0, int ORDER = 1, int W128 = 0,
-          bool REGIONS = false, bool GAP = false, bool ADMA = false, bool PU = true, bool DL = false, int WPB = 4,
-          bool XS = false, bool RD = false, bool NT = false, int PRIO = 0, bool PLAN = false, bool NUM2 = false>
-static hipError_t launch_wstage_t(BatchArgs args, hipStream_t stream) {
-    args.K = wstage_objects_per_wave(NCH, args.A, KCAP);
+// A form: hash_wstage_kernel's template arguments by name, and KCAP, the
+// launcher's cap on objects per wave.  WstageForm holds the defaults; a form
+// derives from the one it varies and overrides what differs.
+struct WstageForm {
+    static constexpr int NCH = 2, SHAPE = 0, HT = 0, ORDER = 1, W128 = 0, WPB = 4, PRIO = 0;
+    static constexpr uint32_t WB = 8832, KCAP = 63;
+    static constexpr bool REGIONS = false, GAP = false, ADMA = false, PU = true, DL = false, XS = false, RD = false,
+                          NT = false, PLAN = false, NUM2 = false;
+};
+// The product (hdx_wstage.hip), and its form for schemas of strings, int64 and floats.
+struct WstageProduct : WstageForm {
+    static constexpr int HT = 6, ORDER = 4, WPB = 1, PRIO = 1;
+    static constexpr bool GAP = true, ADMA = true, XS = true, NT = true;
+};
+struct WstageProductNum2 : WstageProduct {
+    static constexpr int ORDER = 5;
+    static constexpr bool PLAN = true, NUM2 = true;
+};
+template <class F, bool R> struct WithRegions : F { static constexpr bool REGIONS = R; };
+
+template <class F>
+static hipError_t launch_wstage_t(const BatchArgs& args_in, hipStream_t stream) {
+    BatchArgs args = args_in;
+    args.K = wstage_objects_per_wave(F::NCH, args.A, F::KCAP);
     if (args.K == 0) return hipErrorInvalidValue;
-    static_assert(!PLAN || NCH * 64 <= kWavePlanSlots, "the plan covers two passes");
-    if (PLAN) fill_wave_plan(args);
-    if (NUM2 && !num2_schema(args)) return hipErrorInvalidValue;
+    static_assert(!F::PLAN || F::NCH * 64 <= kWavePlanSlots, "the plan covers two passes");
+    if (F::PLAN) fill_wave_plan(args);
+    if (F::NUM2 && !num2_schema(args)) return hipErrorInvalidValue;
     const uint64_t waves = (args.n + args.K - 1) / args.K;
-    const uint64_t blocks = (waves + WPB - 1) / WPB;
+    const uint64_t blocks = (waves + F::WPB - 1) / F::WPB;
     if (blocks == 0) return hipSuccess;
     if (blocks > 0x7fffffffULL) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((hash_wstage_kernel<NCH, WB, SHAPE, HT, ORDER, W128, REGIONS, GAP, ADMA, PU, DL, WPB, XS, RD, NT, PRIO,
-                                           PLAN, NUM2>),
-                       dim3((uint32_t)blocks), dim3(64 * WPB), 0, stream, args);
+    hipLaunchKernelGGL((hash_wstage_kernel<F::NCH, F::WB, F::SHAPE, F::HT, F::ORDER, F::W128, F::REGIONS, F::GAP, F::ADMA,
+                                           F::PU, F::DL, F::WPB, F::XS, F::RD, F::NT, F::PRIO, F::PLAN, F::NUM2>),
+                       dim3((uint32_t)blocks), dim3(64 * F::WPB), 0, stream, args);
     return hipGetLastError();
 }
 

@@ -30,36 +30,24 @@
 
 namespace hdx {
 
-// The product form's geometry: passes of 64 slots per wave, window bytes, the
-// cap on objects per wave, hash_slot's HT (head/tail reads: kFrontHT bytes
-// kept before the window).  The launches below and wstage_product_geometry
-// (hdxdbg_wave_geometry) both read these.
-constexpr int kProductPasses = 2;
-constexpr uint32_t kProductWindow = 8832;
-constexpr uint32_t kProductObjectCap = 63;
-constexpr int kProductHT = 6;
-
+// What a wave of the product form (WstageProduct, hdx_wstage.h) holds:
+// passes of 64 slots, window bytes, the cap on objects per wave, and
+// kFrontHT bytes kept before the window for hash_slot's head/tail reads.
 void wstage_product_geometry(uint32_t A, WaveGeometry& g) {
-    g.objects = wstage_objects_per_wave(kProductPasses, A, kProductObjectCap);  // launch_wstage_t's K
-    g.window = kProductWindow;
+    using P = WstageProduct;
+    g.objects = wstage_objects_per_wave(P::NCH, A, P::KCAP);  // launch_wstage_t's K
+    g.window = P::WB;
     g.key_region = 0;
-    g.front_pad = kProductHT ? kFrontHT : 0;
+    g.front_pad = P::HT ? kFrontHT : 0;
     g.back_pad = kBackW;
-    g.passes = kProductPasses;
-    g.object_cap = wstage_objects_per_wave(kProductPasses, 1, kProductObjectCap);
+    g.passes = P::NCH;
+    g.object_cap = wstage_objects_per_wave(P::NCH, 1, P::KCAP);
 }
 
-// ORDER 5 / 4 (the class from the table / by selects), REGIONS, then GAP, ADMA, PU on, DL off, one wave
-// per workgroup, XS on, RD off, NT on, PRIO 1; the NUM2 form adds PLAN and NUM2
 template <bool REGIONS>
 static hipError_t launch_product_t(const BatchArgs& args, hipStream_t stream) {
-    constexpr int P = kProductPasses, HT = kProductHT;
-    constexpr uint32_t WB = kProductWindow, CAP = kProductObjectCap;
-    if (num2_schema(args))
-        return launch_wstage_t<P, WB, CAP, 0, HT, 5, 0, REGIONS, true, true, true, false, 1, true, false, true, 1,
-                               true, true>(args, stream);
-    return launch_wstage_t<P, WB, CAP, 0, HT, 4, 0, REGIONS, true, true, true, false, 1, true, false, true, 1>(
-        args, stream);
+    if (num2_schema(args)) return launch_wstage_t<WithRegions<WstageProductNum2, REGIONS>>(args, stream);
+    return launch_wstage_t<WithRegions<WstageProduct, REGIONS>>(args, stream);
 }
 
 hipError_t launch_hash_wstage_product(const BatchArgs& args, hipStream_t stream) {

@@ -1,7 +1,10 @@
 // hdx_wstage_dbg.hip — the wave-staged kernel's A/B forms (debug library
-// only, libhdxhash_dbg.so): window sizes and passes per wave, the class sort
-// over the workgroup (hash_wgstage_kernel), debug shapes.  Results: DESIGN.md
-// §4.5 (round 3), profiles/r3/ab_wstage_*.jsonl.
+// only, libhdxhash_dbg.so): each a named variation of another form
+// (WstageForm, hdx_wstage.h), the class sort over the workgroup
+// (hash_wgstage_kernel), debug shapes, and their rows of the batch hash's
+// variant table (hdx_variants.h).  Results: DESIGN.md §4.5 (round 3),
+// profiles/r3/ab_wstage_*.jsonl and the later rounds' profiles.
+#include "hdx_variants.h"
 #include "hdx_wstage.h"
 
 namespace hdx {
@@ -125,65 +128,122 @@ static hipError_t launch_wgstage_t(BatchArgs args, hipStream_t stream) {
 }
 
 
-// form: 0 = 2 passes / 10 KiB windows; 1 = 3 / 14 KiB; 2 = 2 / 8 KiB;
-// 3 = 1 / 5 KiB; 4 = 4 / 18 KiB; 5 = 2 / 8832 B (four workgroups per CU);
-// 6 = form 5 with at most 6 objects per wave.  A wider schema than the form's
-// passes hold (K = 0) returns hipErrorInvalidValue.
-hipError_t launch_hash_wstage(const BatchArgs& args, hipStream_t stream, int form) {
+namespace {
+
+// The forms, named by variant id.  Each says what it changes against the form
+// it derives from; WstageForm and WstageProduct are in hdx_wstage.h.
+// Round 3's first forms: the slots hashed as from global memory (HT 0), four
+// waves per workgroup; passes per wave and window bytes.
+struct V200 : WstageForm { static constexpr uint32_t WB = 10240; };
+struct V201 : WstageForm { static constexpr int NCH = 3; static constexpr uint32_t WB = 14336; };
+struct V202 : WstageForm { static constexpr uint32_t WB = 8192; };
+struct V203 : WstageForm { static constexpr int NCH = 1; static constexpr uint32_t WB = 5120; };
+struct V204 : WstageForm { static constexpr int NCH = 4; static constexpr uint32_t WB = 18432; };
+using V205 = WstageForm;
+struct V206 : V205 { static constexpr uint32_t KCAP = 6; };
+struct V207 : V205 { static constexpr int SHAPE = 1; };
+struct V208 : V205 { static constexpr int SHAPE = 2; };
+struct V209 : V205 { static constexpr uint32_t KCAP = 3; };
+// head/tail window hashing (hash_slot_window)
+struct HeadTail : WstageForm { static constexpr int HT = 1; };
+struct V213 : HeadTail { static constexpr uint32_t KCAP = 3; };
+struct V214 : HeadTail { static constexpr int NCH = 3; static constexpr uint32_t WB = 14336; };
+struct V215 : HeadTail { static constexpr int ORDER = 3; };
+struct V216 : HeadTail { static constexpr int W128 = 1; };
+struct V218 : HeadTail { static constexpr int SHAPE = 1; };
+struct V219 : WstageForm { static constexpr int HT = 2; };
+struct V240 : V219 { static constexpr bool GAP = true; };
+struct V241 : V240 { static constexpr bool ADMA = true; static constexpr int SHAPE = 1; };
+// back from the product, round by round
+struct V287 : WstageProduct { static constexpr int HT = 5; };  // before LOOP 4: round 5's product
+struct V279 : V287 { static constexpr int PRIO = 0; };
+struct V278 : V279 { static constexpr int W128 = 1; };
+struct V270 : V279 { static constexpr bool NT = false; };
+struct V273 : V270 { static constexpr int NCH = 3; static constexpr uint32_t WB = 14336; };
+struct V274 : V270 { static constexpr int NCH = 3; static constexpr uint32_t WB = 13312, KCAP = 10; };
+struct V275 : V270 { static constexpr bool RD = true; };
+struct V276 : V275 { static constexpr uint32_t WB = 8704; };
+struct V256 : V270 { static constexpr bool XS = false; };
+struct V257 : V256 { static constexpr int WPB = 2; };
+struct V258 : V256 { static constexpr uint32_t WB = 7680, KCAP = 6; };
+struct V259 : V256 { static constexpr int WPB = 4; };  // round 4's product
+struct V255 : V259 { static constexpr bool DL = true; };
+struct V248 : V259 { static constexpr int W128 = 2; };
+struct V249 : V259 { static constexpr int W128 = 3; };
+struct V245 : V259 { static constexpr int ORDER = 1; };
+struct V242 : V259 { static constexpr int HT = 3; };
+struct V239 : V259 { static constexpr int HT = 1; };
+struct V246 : V259 { static constexpr int HT = 2; };
+struct V244 : V246 { static constexpr bool PU = false; };
+// round 6: the slot plan (PLAN), numerics by selects (NUM2), the class table (ORDER 5)
+struct V293 : WstageProductNum2 { static constexpr int HT = 5; };
+struct V294 : V287 { static constexpr bool PLAN = true; };
+struct V295 : V287 { static constexpr bool NUM2 = true; };
+struct V296 : V287 { static constexpr int ORDER = 5; };
+struct V297 : V293 { static constexpr int SHAPE = 1; };
+
+// A wider schema than the form's passes hold (K = 0), or one NUM2 does not
+// take, runs the gather kernel 44 instead.
+template <auto LAUNCH>
+hipError_t or_44(const BatchArgs& args, hipStream_t stream) {
     if (args.n == 0) return hipSuccess;
-    switch (form) {
-        case 0: return launch_wstage_t<2, 10240>(args, stream);
-        case 1: return launch_wstage_t<3, 14336>(args, stream);
-        case 2: return launch_wstage_t<2, 8192>(args, stream);
-        case 3: return launch_wstage_t<1, 5120>(args, stream);
-        case 4: return launch_wstage_t<4, 18432>(args, stream);
-        case 5: return launch_wstage_t<2, 8832>(args, stream);
-        case 6: return launch_wstage_t<2, 8832, 6>(args, stream);
-        case 7: return launch_wstage_t<2, 8832, 63, 1>(args, stream);  // debug shape: no hash
-        case 8: return launch_wstage_t<2, 8832, 63, 2>(args, stream);  // debug shape: no DMA
-        case 9: return launch_wstage_t<2, 8832, 3>(args, stream);  // <= 3 objects: per-regime costs on uniform batches
-        // head/tail window hashing (hash_slot_window)
-        case 12: return launch_wstage_t<2, 8832, 63, 0, true>(args, stream);
-        case 13: return launch_wstage_t<2, 8832, 3, 0, true>(args, stream);  // <= 3 objects (per-regime costs)
-        case 14: return launch_wstage_t<3, 14336, 63, 0, true>(args, stream);
-        case 15: return launch_wstage_t<2, 8832, 63, 0, true, 3>(args, stream);  // 12 in class order 3
-        case 16: return launch_wstage_t<2, 8832, 63, 0, true, 1, true>(args, stream);  // 12 with b128 window reads
-        case 18: return launch_wstage_t<2, 8832, 63, 1, true>(args, stream);  // debug shape of 12: no hash (WRONG coordinates)
-        case 19: return launch_wstage_t<2, 8832, 63, 0, 2, 1>(args, stream);  // the product without the pass-boundary gap
-        case 39: return launch_wstage_t<2, 8832, 63, 0, 1, 4, false, false, true, true>(args, stream);  // the product with the one-block loop
-        case 40: return launch_wstage_t<2, 8832, 63, 0, 2, 1, false, false, true>(args, stream);  // the product with the DMA as the builtin
-        case 41: return launch_wstage_t<2, 8832, 63, 1, 2, 1, false, false, true, true>(args, stream);  // debug shape of the product: no hash
-        case 42: return launch_wstage_t<2, 8832, 63, 0, 3, 4, false, false, true, true>(args, stream);  // the product with the shared final mix16
-        case 44: return launch_wstage_t<2, 8832, 63, 0, 2, 4, false, false, true, true, false>(args, stream);  // the product, pass loop not unrolled
-        case 45: return launch_wstage_t<2, 8832, 63, 0, 5, 1, false, false, true, true>(args, stream);  // the product with the branchy class (ORDER 1)
-        case 46: return launch_wstage_t<2, 8832, 63, 0, 2, 4, false, false, true, true>(args, stream);  // the product without TNUM
-        case 48: return launch_wstage_t<2, 8832, 63, 0, 5, 4, 2, false, true, true>(args, stream);  // debug shape: the product's LDS reads conflict-free (WRONG coordinates)
-        case 49: return launch_wstage_t<2, 8832, 63, 0, 5, 4, 3, false, true, true>(args, stream);  // debug shape: no funnel shifts (WRONG coordinates)
-        case 55: return launch_wstage_t<2, 8832, 63, 0, 5, 4, 0, false, true, true, true, true>(args, stream);  // the product with round 3's per-KiB span copy
-        case 56: return launch_wstage_t<2, 8832, 63, 0, 5, 4, 0, false, true, true, true, false, 1>(args, stream);  // the product (one wave per workgroup)
-        case 57: return launch_wstage_t<2, 8832, 63, 0, 5, 4, 0, false, true, true, true, false, 2>(args, stream);  // the product, two waves per workgroup
-        case 58: return launch_wstage_t<2, 7680, 6, 0, 5, 4, 0, false, true, true, true, false, 1>(args, stream);  // <= 6 objects, 7.5 KiB windows: 18 waves per CU
-        case 59: return launch_wstage_t<2, 8832, 63, 0, 5, 4, 0, false, true, true, true, false, 4>(args, stream);  // round 4's product: four waves per workgroup
-        case 70: return launch_wstage_t<2, 8832, 63, 0, 5, 4, 0, false, true, true, true, false, 1, true>(args, stream);  // the product (XCD-aware block order)
-        case 73: return launch_wstage_t<3, 14336, 63, 0, 5, 4, 0, false, true, true, true, false, 1, true>(args, stream);  // 3 passes, 11 objects, 14 KiB
-        case 75: return launch_wstage_t<2, 8832, 63, 0, 5, 4, 0, false, true, true, true, false, 1, true, true>(args, stream);  // descriptors in registers (17 waves per CU)
-        case 76: return launch_wstage_t<2, 8704, 63, 0, 5, 4, 0, false, true, true, true, false, 1, true, true>(args, stream);  // ... with 8.5 KiB windows (18 waves per CU)
-        case 74: return launch_wstage_t<3, 13312, 10, 0, 5, 4, 0, false, true, true, true, false, 1, true>(args, stream);  // 3 passes, 10 objects, 13 KiB
-        case 79: return launch_wstage_t<2, 8832, 63, 0, 5, 4, 0, false, true, true, true, false, 1, true, false, true>(args, stream);  // 70 with non-temporal loads (the product before its wave priorities)
-        case 78: return launch_wstage_t<2, 8832, 63, 0, 5, 4, 1, false, true, true, true, false, 1, true, false, true>(args, stream);  // the product with dword-aligned ds_read_b128 window reads
-        case 87: return launch_wstage_t<2, 8832, 63, 0, 5, 4, 0, false, true, true, true, false, 1, true, false, true, 1>(args, stream);  // the product: 79 with the loads at high wave priority
-        // round 6: the per-schema slot plan (PLAN), numerics by selects (NUM2), the class table (ORDER 5)
-        case 93: return launch_wstage_t<2, 8832, 63, 0, 5, 5, 0, false, true, true, true, false, 1, true, false, true, 1, true, true>(args, stream);  // all three
-        case 94: return launch_wstage_t<2, 8832, 63, 0, 5, 4, 0, false, true, true, true, false, 1, true, false, true, 1, true, false>(args, stream);  // the plan alone
-        case 95: return launch_wstage_t<2, 8832, 63, 0, 5, 4, 0, false, true, true, true, false, 1, true, false, true, 1, false, true>(args, stream);  // NUM2 alone
-        case 96: return launch_wstage_t<2, 8832, 63, 0, 5, 5, 0, false, true, true, true, false, 1, true, false, true, 1, false, false>(args, stream);  // the class table alone
-        case 97: return launch_wstage_t<2, 8832, 63, 1, 5, 5, 0, false, true, true, true, false, 1, true, false, true, 1, true, true>(args, stream);  // debug shape of 93: no hash (WRONG coordinates)
-        case 98: return launch_wstage_t<2, 8832, 63, 0, 5, 5, 0, false, true, true, true, false, 1, true, false, true, 1, true, true>(args, stream);  // the product before LOOP 4 (= 93)
-        // the slots class-sorted over the workgroup
-        case 10: return launch_wgstage_t<2, 8832>(args, stream);
-        case 11: return launch_wgstage_t<1, 4352>(args, stream);
-        default: return hipErrorInvalidValue;
-    }
+    const hipError_t e = LAUNCH(args, stream);
+    return e == hipErrorInvalidValue ? launch_hash_batch_variant(args, stream, 44) : e;
 }
+template <class F>
+constexpr auto form = or_44<launch_wstage_t<F>>;
+
+const BatchRow kRows[] = {
+    {200, form<V200>, "2 passes, 10 KiB windows"},
+    {201, form<V201>, "3 passes, 14 KiB windows"},
+    {202, form<V202>, "2 passes, 8 KiB windows"},
+    {203, form<V203>, "1 pass, 5 KiB windows"},
+    {204, form<V204>, "4 passes, 18 KiB windows"},
+    {205, form<V205>, "2 passes, 8832-byte windows (four workgroups per CU)"},
+    {206, form<V206>, "205 with <= 6 objects per wave"},
+    {207, form<V207>, "debug shape of 205: no hash (WRONG coordinates)"},
+    {208, form<V208>, "debug shape of 205: no DMA (WRONG coordinates)"},
+    {209, form<V209>, "205 with <= 3 objects per wave (per-regime VALU on uniform batches)"},
+    {210, or_44<launch_wgstage_t<2, 8832>>, "the slots class-sorted over the workgroup, 2 passes"},
+    {211, or_44<launch_wgstage_t<1, 4352>>, "... 1 pass, 4352-byte windows"},
+    {213, form<V213>, "head/tail window hashing with <= 3 objects per wave (per-regime costs)"},
+    {214, form<V214>, "head/tail window hashing, 3 passes, 14 KiB windows"},
+    {215, form<V215>, "head/tail window hashing in class order 3"},
+    {216, form<V216>, "head/tail window hashing with b128 window reads"},
+    {218, form<V218>, "debug shape of head/tail window hashing: no hash (WRONG coordinates)"},
+    {219, form<V219>, "round 3's product without the pass-boundary gap (class_sort)"},
+    {239, form<V239>, "259 with the one-block > 64-byte loop (city_gt64_lds LOOP 1)"},
+    {240, form<V240>, "round 3's product with the DMA as the builtin (describe_group ADMA off)"},
+    {241, form<V241>, "debug shape of round 3's product: no hash (WRONG coordinates)"},
+    {242, form<V242>, "259 with one final mix16 for the > 64 and 8..32-byte regimes (LOOP 3)"},
+    {244, form<V244>, "246 with the pass loop not unrolled"},
+    {245, form<V245>, "259 with the branchy work class (ORDER 1)"},
+    {246, form<V246>, "259 without TNUM (numerics read apart from the strings' tail)"},
+    {248, form<V248>, "debug shape of 259: its LDS reads at conflict-free addresses (WRONG coordinates)"},
+    {249, form<V249>, "debug shape of 259: no funnel shifts on its LDS reads (WRONG coordinates)"},
+    {255, form<V255>, "259 with round 3's per-KiB span copy"},
+    {256, form<V256>, "259 with one wave per workgroup"},
+    {257, form<V257>, "259 with two waves per workgroup"},
+    {258, form<V258>, "256 with <= 6 objects and 7.5 KiB windows: 18 waves per CU"},
+    {259, form<V259>, "round 4's product: four waves per workgroup"},
+    {270, form<V270>, "256 with the XCD-aware block order"},
+    {273, form<V273>, "270 with 3 passes, 11 objects per wave, 14 KiB windows"},
+    {274, form<V274>, "270 with 3 passes, 10 objects per wave, 13 KiB windows"},
+    {275, form<V275>, "270 with its descriptors in registers (17 waves per CU)"},
+    {276, form<V276>, "275 with 8.5 KiB windows (18 waves per CU)"},
+    {278, form<V278>, "279 with dword-aligned ds_read_b128 window reads (W128 1)"},
+    {279, form<V279>, "270 with non-temporal loads (lengths, bases, span)"},
+    {287, form<V287>, "279 with wave priorities, loads high: round 5's product, the product before LOOP 4"},
+    {293, form<V293>, "287 with the slot plan, select numerics and the class table"},
+    {294, form<V294>, "287 with the slot plan alone"},
+    {295, form<V295>, "287 with select numerics (NUM2) alone"},
+    {296, form<V296>, "287 with the class table alone"},
+    {297, form<V297>, "debug shape of 293: no hash (WRONG coordinates)"},
+    {298, form<V293>, "the product as before LOOP 4 (two head reads, separate mix16s; = 293)"},
+};
+
+}  // namespace
+
+VariantRows<BatchArgs> wstage_variant_rows() { return kRows; }
 
 }  // namespace hdx

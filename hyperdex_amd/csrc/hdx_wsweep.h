@@ -457,20 +457,46 @@ static bool num2_codes(const EncodedArgs& a) {
     return true;
 }
 
-template <int NCH, uint32_t WB, uint32_t KCAP, bool REGIONS = false, bool GAP = false, int SHAPE = 0, int LOOP = 1,
-          bool ASM = false, bool PU = true, bool BF = false, bool RECS = true, bool KUNITS = true, bool DL = false,
-          int WPB = 4, bool XS = false, int PRIO = 0, bool NUM2 = false>
+// A form: hash_sweep_wstage_kernel's template arguments by name.  WsweepForm
+// holds the defaults (round 3's geometry); a form derives from the one it
+// varies and overrides what differs.
+struct WsweepForm {
+    static constexpr int NCH = 2, SHAPE = 0, LOOP = 1, WPB = 4, PRIO = 0;
+    static constexpr uint32_t WB = 8704, KCAP = 6;
+    static constexpr bool REGIONS = false, GAP = false, ASM = false, PU = true, BF = false, RECS = true, KUNITS = true,
+                          DL = false, XS = false, NUM2 = false;
+};
+// The product (hdx_wsweep.hip), and its form for schemas of strings, int64 and floats.
+struct WsweepProduct : WsweepForm {
+    static constexpr uint32_t WB = 9728, KCAP = 7;
+    static constexpr int LOOP = 14, WPB = 1, PRIO = 4;
+    static constexpr bool GAP = true, BF = true, XS = true;
+};
+struct WsweepProductNum2 : WsweepProduct {
+    static constexpr bool NUM2 = true;
+};
+template <class F, bool R> struct WithSweepRegions : F { static constexpr bool REGIONS = R; };
+template <class F, bool R> struct WithRecords : F { static constexpr bool RECS = R; };
+
+template <class F>
 static hipError_t launch_wsweep_t(const EncodedArgs& a, hipStream_t stream) {
-    const uint32_t K = wsweep_objects_per_wave(NCH, a.A, KCAP);
+    const uint32_t K = wsweep_objects_per_wave(F::NCH, a.A, F::KCAP);
     if (K == 0) return hipErrorInvalidValue;
-    if (NUM2 && !num2_codes(a)) return hipErrorInvalidValue;
+    if (F::NUM2 && !num2_codes(a)) return hipErrorInvalidValue;
     const uint64_t waves = (a.n + K - 1) / K;
-    const uint64_t blocks = (waves + WPB - 1) / WPB;
+    const uint64_t blocks = (waves + F::WPB - 1) / F::WPB;
     if (blocks > 0x7fffffffULL) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((hash_sweep_wstage_kernel<NCH, WB, KCAP, REGIONS, GAP, SHAPE, LOOP, ASM, PU, BF, RECS, KUNITS, DL, WPB, XS, PRIO,
-                                                 NUM2>),
-                       dim3((uint32_t)blocks), dim3(64 * WPB), 0, stream, a);
+    hipLaunchKernelGGL((hash_sweep_wstage_kernel<F::NCH, F::WB, F::KCAP, F::REGIONS, F::GAP, F::SHAPE, F::LOOP, F::ASM, F::PU,
+                                                 F::BF, F::RECS, F::KUNITS, F::DL, F::WPB, F::XS, F::PRIO, F::NUM2>),
+                       dim3((uint32_t)blocks), dim3(64 * F::WPB), 0, stream, a);
     return hipGetLastError();
+}
+
+// The record span is compiled in only when keys and values are one store.
+template <class F>
+static hipError_t by_store_layout(const EncodedArgs& a, hipStream_t stream) {
+    return a.keys == a.vals ? launch_wsweep_t<WithRecords<F, true>>(a, stream)
+                            : launch_wsweep_t<WithRecords<F, false>>(a, stream);
 }
 
 }  // namespace hdx

@@ -33,38 +33,30 @@ namespace hdx {
 // read per slot in a pass holding long and short strings): 3.247 vs 3.266 and
 // 3.261 vs 3.287 ms per 10 M on the key column (debug 298 = LOOP 13,
 // profiles/r6/ab_loop4.jsonl).
-// The product form's geometry: passes of 64 slots per wave, window bytes, the
-// cap on objects per wave.  The launch below and wsweep_product_geometry
-// (hdxdbg_wave_geometry) both read these.
-constexpr int kProductPasses = 2;
-constexpr uint32_t kProductWindow = 9728;
-constexpr uint32_t kProductObjectCap = 7;
-
+// What a wave of the product form (WsweepProduct, hdx_wsweep.h) holds: passes
+// of 64 slots, window bytes, the cap on objects per wave.
 void wsweep_product_geometry(uint32_t A, WaveGeometry& g) {
-    g.objects = wsweep_objects_per_wave(kProductPasses, A, kProductObjectCap);  // the kernel's and the launcher's K
-    g.window = kProductWindow;
-    g.key_region = kProductWindow / kKeyRegionDiv;
+    using P = WsweepProduct;
+    g.objects = wsweep_objects_per_wave(P::NCH, A, P::KCAP);  // the kernel's and the launcher's K
+    g.window = P::WB;
+    g.key_region = P::WB / kKeyRegionDiv;
     g.front_pad = kFrontS;
     g.back_pad = kBackS;
-    g.passes = kProductPasses;
-    g.object_cap = kProductObjectCap;
+    g.passes = P::NCH;
+    g.object_cap = P::KCAP;
 }
 
-template <bool REG, bool RECS>
+template <bool REGIONS>
 static hipError_t launch_wsweep_product_t(const EncodedArgs& a, hipStream_t stream) {
-    constexpr int P = kProductPasses;
-    constexpr uint32_t WB = kProductWindow, CAP = kProductObjectCap;
-    if (num2_codes(a))
-        return launch_wsweep_t<P, WB, CAP, REG, true, 0, 14, false, true, true, RECS, true, false, 1, true, 4, true>(a, stream);
-    return launch_wsweep_t<P, WB, CAP, REG, true, 0, 14, false, true, true, RECS, true, false, 1, true, 4>(a, stream);
+    if (num2_codes(a)) return by_store_layout<WithSweepRegions<WsweepProductNum2, REGIONS>>(a, stream);
+    return by_store_layout<WithSweepRegions<WsweepProduct, REGIONS>>(a, stream);
 }
 
 hipError_t launch_hash_wsweep_product(const EncodedArgs& a, hipStream_t stream) {
     if (a.n == 0) return hipSuccess;
-    const bool recs = a.keys == a.vals;
-    if (a.T) return recs ? launch_wsweep_product_t<true, true>(a, stream) : launch_wsweep_product_t<true, false>(a, stream);
+    if (a.T) return launch_wsweep_product_t<true>(a, stream);
     if (!a.coords) return hipErrorInvalidValue;
-    return recs ? launch_wsweep_product_t<false, true>(a, stream) : launch_wsweep_product_t<false, false>(a, stream);
+    return launch_wsweep_product_t<false>(a, stream);
 }
 
 }  // namespace hdx

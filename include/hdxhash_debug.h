@@ -7,8 +7,8 @@
  * hdxdbg_region_chunk_objects (tests/test_scale.py's chunk edges) and
  * hdxdbg_wave_geometry (tests/test_window_edges.py's window boundaries).
  * libhdxhash_dbg.so only (HDX_DEBUG_BUILD, hyperdex_amd/csrc/Makefile):
- * hdxdbg_set_kernel_variant / hdxdbg_kernel_variant, used by
- * scripts/ab_variants.py and the variant parity tests.  The product library
+ * hdxdbg_set_kernel_variant / hdxdbg_kernel_variant / hdxdbg_variant_entries,
+ * used by scripts/ab_variants.py and the variant parity tests.  The product library
  * has no kernel selection and no environment switches.
  */
 #ifndef HDXHASH_DEBUG_H
@@ -26,6 +26,16 @@ extern "C" {
  * changed). */
 int hdxdbg_set_kernel_variant(int variant);
 int hdxdbg_kernel_variant(void);
+/* [debug library only] Where a variant id selects something: a mask of the
+ * entry points at which it has a row in the variant table (the other entry
+ * points keep their automatic policy under it), HDXDBG_ENTRY_POLICY for an id
+ * that switches a policy instead of a kernel; -2 for an unknown id. */
+#define HDXDBG_ENTRY_BATCH 1          /* hdx_hash_batch_device */
+#define HDXDBG_ENTRY_BATCH_REGIONS 2  /* hdx_hash_batch_regions_device, A <= 128 */
+#define HDXDBG_ENTRY_SWEEP 4          /* hdx_hash_encoded_device, A <= 128 */
+#define HDXDBG_ENTRY_WIDE_SWEEP 8     /* hdx_hash_encoded_device, wide schemas */
+#define HDXDBG_ENTRY_POLICY 16
+int hdxdbg_variant_entries(int variant);
 /* The variant hdx_hash_batch_device would launch for this schema and object
  * count (under the current selection), and the kernel's symbol as rocprofv3
  * reports it (*name; static string).  Returns -2 on a bad schema. */

@@ -126,6 +126,84 @@ def test_variant_hook():
     assert lib.hdxdbg_set_kernel_variant(cur) == 12
 
 
+ENTRY_BATCH, ENTRY_BATCH_REGIONS, ENTRY_SWEEP, ENTRY_WIDE_SWEEP, ENTRY_POLICY = 1, 2, 4, 8, 16  # hdxhash_debug.h
+
+
+def _ids(spec):
+    out = []
+    for part in spec.replace(" ", "").split(","):
+        lo, _, hi = part.rpartition("-") if "-" in part[1:] else ("", "", part)
+        out += range(int(lo or hi), int(hi) + 1)
+    return out
+
+
+# every id hdxdbg_set_kernel_variant accepts (137), as before the variant tables
+ACCEPTED = _ids("-1, 12, 18-21, 25, 26, 30, 31, 33, 35, 37-41, 43-49, 57, 58, 100-111, 170-174, 200-219, 230-265, "
+                "270-287, 293-298, 300, 301, 304-315")
+
+
+def test_variant_hook_accepts_exactly_the_known_ids():
+    lib = _lib.debug_lib()
+    cur = lib.hdxdbg_kernel_variant()
+    got = []
+    try:
+        for v in range(-5, 1000):
+            if lib.hdxdbg_set_kernel_variant(v) != -2:
+                got.append(v)
+                assert lib.hdxdbg_kernel_variant() == v
+    finally:
+        lib.hdxdbg_set_kernel_variant(cur)
+    assert len(ACCEPTED) == 137 and got == ACCEPTED
+
+
+def test_every_accepted_variant_selects_something():
+    """An accepted id has a row in some entry point's table or is a policy
+    switch; any other id is unknown to both hooks."""
+    lib = _lib.debug_lib()
+    for v in range(-5, 1000):
+        mask = lib.hdxdbg_variant_entries(v)
+        if v in ACCEPTED:
+            assert 0 < mask < 32 or v == -1, (v, mask)
+        else:
+            assert mask == -2, (v, mask)
+    assert lib.hdxdbg_variant_entries(-1) in (0, ENTRY_POLICY)
+
+
+def _forced_ids(module, test, arg="variant"):
+    """The ids a GPU parity test forces: its own parametrize list."""
+    marks = [m for m in getattr(module, test).pytestmark if m.name == "parametrize" and m.args[0] == arg]
+    assert len(marks) == 1, (test, arg)
+    return [v for v in marks[0].args[1] if v >= 0]
+
+
+def test_parity_tests_force_ids_wired_at_their_entry_point():
+    """A forced id without a row at the entry point a test calls runs the
+    product kernel there, and the parity test passes without testing the
+    form it names: every id the GPU parity tests force must select something
+    at that test's entry point."""
+    import test_encoded
+    import test_gpu_parity
+    import test_regions
+    import test_wide
+    lib = _lib.debug_lib()
+    batch = set(test_gpu_parity.VARIANTS)
+    for t in ("test_bad_size_every_variant", "test_wave_staged_layouts", "test_wave_staged_long_strings",
+              "test_every_kernel_variant_matches_oracle"):
+        batch |= set(_forced_ids(test_gpu_parity, t))
+    sweep = set()
+    for t in ("test_gpu_encoded_scattered_layout", "test_gpu_encoded_every_variant",
+              "test_gpu_encoded_bad_numeric_size", "test_gpu_encoded_regions_fused", "test_gpu_encoded_records"):
+        sweep |= set(_forced_ids(test_encoded, t))
+    sweep |= {235, 247}  # test_encoded.py's and test_regions.py's "chunks" / "no_scratch" cases
+    wide = set(_forced_ids(test_wide, "test_gpu_sweep_stream_ring"))
+    fused = set(_forced_ids(test_regions, "test_gpu_batch_regions_every_fused_form", "form"))
+    assert len(batch) > 60 and len(sweep) > 40 and len(wide) == 7 and fused == set(range(100, 112)) | {217}
+    for ids, need in ((batch, ENTRY_BATCH | ENTRY_POLICY), (sweep, ENTRY_SWEEP | ENTRY_WIDE_SWEEP | ENTRY_POLICY),
+                      (wide, ENTRY_WIDE_SWEEP), (fused, ENTRY_BATCH_REGIONS)):
+        unwired = sorted(v for v in ids if not lib.hdxdbg_variant_entries(v) & need or lib.hdxdbg_variant_entries(v) < 0)
+        assert not unwired, (unwired, need)
+
+
 def test_kernel_for_reports_the_auto_policy():
     """hdxdbg_kernel_for: the variant/kernel the automatic policy picks per
     schema, with no device needed."""

@@ -302,7 +302,7 @@ def test_gpu_regions_scratch_pool_across_calls_and_shutdown(oracle):
 @pytest.mark.gpu
 @pytest.mark.parametrize("form", list(range(100, 112)) + [217])
 def test_gpu_batch_regions_every_fused_form(oracle, form):
-    """The debug library's fused forms (hdx_kernels_dbg.hip launch_fused_debug:
+    """The debug library's fused forms (hdx_kernels_dbg.hip kBatchRegionsRows:
     chunks per wave, sorted or not, tables in LDS or global memory, the
     per-lane or wave-uniform table loop) all give the oracle's region ids."""
     import torch
