@@ -365,7 +365,6 @@ HDX_EXPORT hdx_status hdx_hash_batch_device(const uint32_t* types, uint32_t attr
                                             const uint32_t* attr_len, uint64_t n,
                                             uint64_t* coords, uint32_t* status_dev,
                                             hdx_stream stream) {
-    BatchArgs args{};
     std::vector<uint8_t> codes(attrs_sz ? attrs_sz : 1);
     hdx_status st = check_schema(types, attrs_sz, codes.data());
     if (st != HDX_OK) return st;
@@ -373,17 +372,11 @@ HDX_EXPORT hdx_status hdx_hash_batch_device(const uint32_t* types, uint32_t attr
     if (!blob || !obj_base || !attr_len || !coords)
         return fail(HDX_E_INVALID, "NULL device pointer");
     if ((st = bind_device(-1)) != HDX_OK) return st;
-    if ((st = set_codes(args, codes.data(), attrs_sz)) != HDX_OK) return st;
-    hipStream_t s = (hipStream_t)stream;  // NULL = the HIP null stream
-    args.blob = blob;
-    args.obj_base = obj_base;
-    args.attr_len = attr_len;
-    args.coords = coords;
-    args.status = status_dev;
-    args.n = n;
-    args.A = attrs_sz;
-    finalize_args(args);
-    HIP_TRY(launch_hash_batch(args, s));
+    BatchArgs args;
+    if ((st = batch_args(args, codes.data(), attrs_sz, blob, obj_base, attr_len, n, coords, status_dev, nullptr, 0,
+                         nullptr, 0, t_state.device)) != HDX_OK)
+        return st;
+    HIP_TRY(launch_hash_batch(args, (hipStream_t)stream));  // NULL = the HIP null stream
     return HDX_OK;
 }
 
@@ -401,14 +394,12 @@ hdx_status fill_sweep_table(SweepTable& st, hdx_region_table_s* t, int dev, uint
             if (x.device == dev) r = &x;
         if (!r) {
             hdx_region_table_s::Replica c{dev, nullptr, nullptr, nullptr, nullptr};
-            const size_t box = t->h_lower.size() * 8;
             auto up = [](uint64_t** d, const std::vector<uint64_t>& h, size_t extra) {
                 if (hipMalloc((void**)d, h.size() * 8 + extra) != hipSuccess) return false;
                 return h.empty() || hipMemcpy(*d, h.data(), h.size() * 8, hipMemcpyHostToDevice) == hipSuccess;
             };
             const bool ok = up(&c.lower, t->h_lower, 8) && up(&c.upper, t->h_upper, 8) && up(&c.ids, t->h_ids, 8) &&
                             (t->h_index.empty() || !t->d_index || up(&c.index, t->h_index, 0));
-            (void)box;
             if (!ok) {
                 (void)hipGetLastError();
                 (void)hipFree(c.lower); (void)hipFree(c.upper); (void)hipFree(c.ids); (void)hipFree(c.index);
@@ -437,7 +428,6 @@ static hdx_status hash_encoded(const uint32_t* types, uint32_t attrs_sz, const u
                                const uint64_t* val_off, const uint32_t* val_len, uint64_t n,
                                const hdx_region_table* tables, uint32_t ntables, uint64_t* region_ids,
                                uint64_t* coords, uint64_t* versions, uint32_t* status_dev, hdx_stream stream) {
-    EncodedArgs a{};
     std::vector<uint8_t> codes(attrs_sz ? attrs_sz : 1);
     hdx_status st = check_schema(types, attrs_sz, codes.data());
     if (st != HDX_OK) return st;
@@ -446,21 +436,10 @@ static hdx_status hash_encoded(const uint32_t* types, uint32_t attrs_sz, const u
     if (!keys || !key_off || !key_len || !vals || !val_off || !val_len || (!coords && !ntables))
         return fail(HDX_E_INVALID, "NULL device pointer");
     if ((st = bind_device(-1)) != HDX_OK) return st;
-    if ((st = set_codes(a, codes.data(), attrs_sz)) != HDX_OK) return st;
-    a.T = ntables;
-    for (uint32_t t = 0; t < ntables; ++t)
-        if ((st = fill_sweep_table(a.t[t], tables[t], t_state.device, region_ids + (size_t)t * n)) != HDX_OK) return st;
-    a.keys = keys;
-    a.key_off = key_off;
-    a.key_len = key_len;
-    a.vals = vals;
-    a.val_off = val_off;
-    a.val_len = val_len;
-    a.coords = coords;
-    a.versions = versions;
-    a.status = status_dev;
-    a.n = n;
-    a.A = attrs_sz;
+    EncodedArgs a;
+    if ((st = encoded_args(a, codes.data(), attrs_sz, keys, key_off, key_len, vals, val_off, val_len, n, coords,
+                           versions, status_dev, tables, ntables, region_ids, n, t_state.device)) != HDX_OK)
+        return st;
     HIP_TRY(launch_hash_encoded(a, (hipStream_t)stream));
     return HDX_OK;
 }
@@ -525,6 +504,31 @@ hdx_status batch_args(BatchArgs& args, const uint8_t* codes, uint32_t A, const u
     args.T = T;
     for (uint32_t t = 0; t < T; ++t)
         if ((st = fill_sweep_table(args.t[t], tables[t], dev, ids + t * ids_stride)) != HDX_OK) return st;
+    return HDX_OK;
+}
+
+hdx_status encoded_args(EncodedArgs& a, const uint8_t* codes, uint32_t A, const uint8_t* keys,
+                        const uint64_t* key_off, const uint32_t* key_len, const uint8_t* vals,
+                        const uint64_t* val_off, const uint32_t* val_len, uint64_t n, uint64_t* coords,
+                        uint64_t* versions, uint32_t* status, const hdx_region_table* tables, uint32_t T,
+                        uint64_t* ids, uint64_t ids_stride, int dev) {
+    a = EncodedArgs{};
+    hdx_status st = set_codes(a, codes, A);
+    if (st != HDX_OK) return st;
+    a.keys = keys;
+    a.key_off = key_off;
+    a.key_len = key_len;
+    a.vals = vals;
+    a.val_off = val_off;
+    a.val_len = val_len;
+    a.coords = coords;
+    a.versions = versions;
+    a.status = status;
+    a.n = n;
+    a.A = A;
+    a.T = T;
+    for (uint32_t t = 0; t < T; ++t)
+        if ((st = fill_sweep_table(a.t[t], tables[t], dev, ids + t * ids_stride)) != HDX_OK) return st;
     return HDX_OK;
 }
 }  // namespace hdx

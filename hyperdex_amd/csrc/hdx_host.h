@@ -71,6 +71,12 @@ hdx_status batch_args(BatchArgs& args, const uint8_t* codes, uint32_t A, const u
                       const uint64_t* obj_base, const uint32_t* attr_len, uint64_t n, uint64_t* coords,
                       uint32_t* status, const hdx_region_table* tables, uint32_t T, uint64_t* ids,
                       uint64_t ids_stride, int dev);
+// The same for stored objects (the sweep).
+hdx_status encoded_args(EncodedArgs& a, const uint8_t* codes, uint32_t A, const uint8_t* keys,
+                        const uint64_t* key_off, const uint32_t* key_len, const uint8_t* vals,
+                        const uint64_t* val_off, const uint32_t* val_len, uint64_t n, uint64_t* coords,
+                        uint64_t* versions, uint32_t* status, const hdx_region_table* tables, uint32_t T,
+                        uint64_t* ids, uint64_t ids_stride, int dev);
 // Device scratch owned by the library (per-thread staging and streams),
 // registered so hdx_shutdown can free every thread's (track_scratch /
 // untrack_scratch; release() must leave the object reusable).
@@ -107,27 +113,54 @@ struct DevBuf {  // hipMalloc'd
     T* p = nullptr;
     size_t cap = 0;
     hdx_status need(size_t n) { return grow_dev(&p, &cap, n); }
+    void release() {
+        (void)hipFree(p);
+        *this = DevBuf{};
+    }
 };
 template <typename T>
 struct PinBuf {  // hipHostMalloc'd
     T* p = nullptr;
     size_t cap = 0;
     hdx_status need(size_t n) { return grow_pinned(&p, &cap, n); }
+    void release() {
+        (void)hipHostFree(p);
+        *this = PinBuf{};
+    }
 };
+// A slot's buffers, each declared here once: X(type, name) is a device buffer
+// d_<name> and a pinned one h_<name> (inputs: filled only when the caller's
+// array is pageable or the chunk is rebased or packed; outputs: only for
+// pageable destinations).  The packed and the stored pipeline never hold a
+// slot at the same time and share the buffers of one role.
+#define HDX_SLOT_BUFFERS(X)                                                                    \
+    X(uint8_t, blob)    /* packed blob; stored values, records, or packed records */          \
+    X(uint8_t, keys)    /* the key column's span */                                            \
+    X(uint64_t, off)    /* the chunk's object bases / key offsets */                           \
+    X(uint64_t, voff)   /* value offsets */                                                    \
+    X(uint32_t, len)    /* attribute lengths / key lengths */                                  \
+    X(uint32_t, vlen)   /* value lengths */                                                    \
+    X(uint64_t, coords) /* outputs */                                                          \
+    X(uint64_t, ids)                                                                           \
+    X(uint64_t, ver)                                                                           \
+    X(uint32_t, status) /* the sweep's status word */                                          \
+    X(uint64_t, src)    /* packed chunks (objects out of address order): the extents' */      \
+    X(uint32_t, sz)     /* sources, lengths and destination offsets for the gather */         \
+    X(uint64_t, dst)    /* kernel (hdx_gather.hip) */
 struct HostSlot {
     hipStream_t s = nullptr;
-    DevBuf<uint8_t> d_blob, d_keys;       // packed blob or stored values (records: keys too); keys
-    DevBuf<uint64_t> d_base, d_coords, d_ids, d_koff, d_voff, d_ver;
-    DevBuf<uint32_t> d_len, d_klen, d_vlen, d_status;
-    PinBuf<uint8_t> h_blob, h_keys;       // only for pageable inputs
-    PinBuf<uint64_t> h_base, h_coords, h_ids, h_koff, h_voff, h_ver;
-    PinBuf<uint32_t> h_len, h_klen, h_vlen, h_status;
-    // packed chunks (objects out of address order): the extents' source
-    // offsets and lengths for the gather kernel (hdx_gather.hip)
-    DevBuf<uint64_t> d_src, d_src2;
-    DevBuf<uint32_t> d_sz, d_sz2;
-    PinBuf<uint64_t> h_src, h_src2;
-    PinBuf<uint32_t> h_sz, h_sz2;
+#define HDX_SLOT_DECLARE(T, name) \
+    DevBuf<T> d_##name;           \
+    PinBuf<T> h_##name;
+    HDX_SLOT_BUFFERS(HDX_SLOT_DECLARE)
+#undef HDX_SLOT_DECLARE
+    void release_buffers() {
+#define HDX_SLOT_RELEASE(T, name) \
+    d_##name.release();           \
+    h_##name.release();
+        HDX_SLOT_BUFFERS(HDX_SLOT_RELEASE)
+#undef HDX_SLOT_RELEASE
+    }
 };
 // The device view of pinned host memory p (for a kernel to read it), or NULL
 // when p is not pinned.

@@ -7,44 +7,28 @@
 // daemon/datalayer.cc:853-882).
 //
 // One device's pipeline (hash_host, hash_encoded_host) streams the call
-// through its two slots in chunks of at most kChunkBytes: host validation of
-// the chunk, H2D of its span(s) and rebased offsets, the kernel(s), D2H of the
+// through its two slots in chunks (hdx_chunks.h): host validation of the
+// chunk, H2D of its span(s) and rebased offsets, the kernel(s), D2H of the
 // outputs — the two slots' streams overlap one chunk's copies with the
-// other's kernel.  hdx_multi.cpp splits a call over the device set and runs
-// one pipeline per device (hash_host_any / hash_encoded_host_any).
+// other's kernel.  One driver (run_chunks) owns the slots and the chunks in
+// flight; a source per kind of input (PackedSource, StoredSource) validates
+// the objects, uploads a chunk and launches its kernel.  hdx_multi.cpp splits
+// a call over the device set and runs one pipeline per device (hash_host_any /
+// hash_encoded_host_any).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstring>
 #include <vector>
 
+#include "hdx_chunks.h"
 #include "hdx_host.h"
 
 namespace hdx {
 
-static constexpr uint64_t kChunkBytes = 128ull << 20;  // payload bytes per in-flight chunk
-// A chunk packed on the device (hdx_gather.hip) grows to this: its two slots'
-// kernels share one hardware queue, so each chunk pays ~0.5 ms of queue
-// turnaround between its gather and the next (profiles/r6/host_order_trace.txt);
-// larger chunks amortise it (device staging only: no pinned copy)
-static constexpr uint64_t kPackChunkBytes = 512ull << 20;
-// A call's first chunk: small, so the first copy starts after a few
-// milliseconds less of host-side validation (later chunks are validated while
-// the previous ones move)
-static constexpr uint64_t kFirstChunkBytes = 16ull << 20;
-
 void free_host_slot(HostSlot& s) {
     if (s.s) (void)hipStreamSynchronize(s.s);
-    for (void* p : {(void*)s.d_blob.p, (void*)s.d_keys.p, (void*)s.d_base.p, (void*)s.d_coords.p, (void*)s.d_ids.p,
-                    (void*)s.d_koff.p, (void*)s.d_voff.p, (void*)s.d_ver.p, (void*)s.d_len.p, (void*)s.d_klen.p,
-                    (void*)s.d_vlen.p, (void*)s.d_status.p, (void*)s.d_src.p, (void*)s.d_src2.p, (void*)s.d_sz.p,
-                    (void*)s.d_sz2.p})
-        (void)hipFree(p);
-    for (void* p : {(void*)s.h_blob.p, (void*)s.h_keys.p, (void*)s.h_base.p, (void*)s.h_coords.p, (void*)s.h_ids.p,
-                    (void*)s.h_koff.p, (void*)s.h_voff.p, (void*)s.h_ver.p, (void*)s.h_len.p, (void*)s.h_klen.p,
-                    (void*)s.h_vlen.p, (void*)s.h_status.p, (void*)s.h_src.p, (void*)s.h_src2.p, (void*)s.h_sz.p,
-                    (void*)s.h_sz2.p})
-        (void)hipHostFree(p);
+    s.release_buffers();
     if (s.s) (void)hipStreamDestroy(s.s);
     s = HostSlot{};
 }
@@ -61,22 +45,47 @@ const uint8_t* device_view(const uint8_t* p) {
     return (const uint8_t*)a.devicePointer + (p - (const uint8_t*)a.hostPointer);
 }
 
-// A chunk whose objects' byte span is no more than this much over their
-// payload goes as one span copy (no gather); otherwise its objects are packed
-// in index order (hdx_gather.hip for pinned sources, a host copy per object
-// for pageable ones), so a batch in any order moves only its own bytes.
-static bool span_pays(uint64_t span, uint64_t payload) {
-    return span <= kChunkBytes && span <= payload + payload / 8 + (64u << 10);
+namespace {
+
+// The host source of an H2D copy of p[0, count): the caller's array when it
+// is pinned, else a copy of it in pinned staging.
+template <typename T>
+hdx_status pinned_or_staged(const T* p, bool pinned, PinBuf<T>& buf, uint64_t count, const T** src) {
+    *src = p;
+    if (pinned) return HDX_OK;
+    const hdx_status st = buf.need(std::max<uint64_t>(count, 1));
+    if (st != HDX_OK) return st;
+    std::memcpy(buf.p, p, count * sizeof(T));
+    *src = buf.p;
+    return HDX_OK;
 }
 
-// In the pipelines' loops: a HIP error lets the copies in flight land first.
-#define DRAIN_TRY(expr)                                          \
-    do {                                                         \
-        hipError_t e_ = (expr);                                  \
-        if (e_ != hipSuccess) return drain(hip_fail(e_, #expr)); \
-    } while (0)
-
-namespace {
+// A chunk's small arrays (offsets, lengths, gather extents), host to device.
+// by_kernel (a chunk the device packs): one copy kernel through the sources'
+// device views when each has one, so that every input of the chunk is moved by
+// the compute queue and the gather waits on no SDMA copy; else a copy each.
+struct SmallCopy {
+    const void* src;
+    void* dst;
+    uint64_t bytes;
+};
+hdx_status copy_small(const SmallCopy* c, uint32_t count, bool by_kernel, hipStream_t s) {
+    const void* src[8];
+    void* dst[8];
+    uint64_t bytes[8];
+    for (uint32_t x = 0; by_kernel && x < count; ++x) {
+        src[x] = device_view((const uint8_t*)c[x].src);
+        dst[x] = c[x].dst;
+        bytes[x] = c[x].bytes;
+        by_kernel = src[x] != nullptr;
+    }
+    if (by_kernel) {
+        HIP_TRY(launch_copy_linear(src, dst, bytes, count, s));
+        return HDX_OK;
+    }
+    for (uint32_t x = 0; x < count; ++x) HIP_TRY(hipMemcpyAsync(c[x].dst, c[x].src, c[x].bytes, hipMemcpyHostToDevice, s));
+    return HDX_OK;
+}
 
 // One chunk in flight on a slot: where its outputs go once it lands.
 struct Pending {
@@ -94,6 +103,11 @@ struct Outputs {
     bool ids_pinned;
     uint64_t* versions = nullptr;  // stored objects only
     bool versions_pinned = false;
+
+    Outputs(uint32_t A_, uint64_t* coords_, const HostRegions* R_, uint64_t* versions_ = nullptr)
+        : A(A_), coords(coords_), coords_pinned(coords_ && is_pinned(coords_)), R(R_),
+          ids_pinned(R_ && R_->T && is_pinned(R_->ids)), versions(versions_),
+          versions_pinned(versions_ && is_pinned(versions_)) {}
 
     uint32_t T() const { return R ? R->T : 0; }
     // D2H of a chunk's outputs on the slot's stream
@@ -133,22 +147,76 @@ struct Outputs {
     }
 };
 
-}  // namespace
+// The pipeline of one call on the calling thread's two slots (thread_slots,
+// taken before the source is built: it binds the thread).  Per chunk:
+// wait for the slot's previous chunk and land its outputs, then the source's
+// upload (grow the slot's buffers, host-side staging, H2D) and launch (the
+// kernel into d_coords / d_ids / d_ver), then the outputs' D2H.  Host
+// validation of the next chunk (next_chunk -> src.object) runs while both
+// slots' chunks move.  status_bits (stored objects; else NULL) receives the OR
+// of the chunks' device status words, d_status -> h_status.  Any failure lets
+// every copy in flight land before it returns.
+template <typename Source>
+hdx_status run_chunks(HostSlot* slots, Source& src, uint64_t n, const Outputs& out, uint32_t* status_bits) {
+    hdx_status st;
+    Pending pend[2];
+    auto finish = [&](int k) -> hdx_status {
+        if (!pend[k].live) return HDX_OK;
+        pend[k].live = false;
+        HIP_TRY(hipStreamSynchronize(slots[k].s));
+        out.land(slots[k], pend[k].first, pend[k].cnt);
+        if (status_bits) *status_bits |= *slots[k].h_status.p;
+        return HDX_OK;
+    };
+    auto drain = [&](hdx_status err) {
+        for (int q = 0; q < 2; ++q) {
+            (void)finish(q);
+            (void)hipStreamSynchronize(slots[q].s);
+        }
+        return err;
+    };
+    auto status_back = [&](HostSlot& sl) -> hdx_status {
+        if (status_bits) HIP_TRY(hipMemcpyAsync(sl.h_status.p, sl.d_status.p, 4, hipMemcpyDeviceToHost, sl.s));
+        return HDX_OK;
+    };
+    ChunkCursor cur;
+    Chunk c;
+    int k = 0;
+    for (;; k ^= 1) {
+        if ((st = next_chunk(src, n, src.device_packs(), cur, c)) != HDX_OK) return drain(st);
+        if (c.cnt == 0) break;
+        HostSlot& sl = slots[k];
+        if ((st = finish(k)) != HDX_OK || (st = src.upload(sl, c)) != HDX_OK || (st = src.launch(sl, c)) != HDX_OK ||
+            (st = out.copy_back(sl, c.first, c.cnt)) != HDX_OK || (st = status_back(sl)) != HDX_OK)
+            return drain(st);
+        pend[k] = {true, c.first, c.cnt};
+    }
+    if ((st = finish(k)) != HDX_OK) return drain(st);
+    return finish(k ^ 1);
+}
 
 // ---- packed batches ---------------------------------------------------------------
 
-hdx_status hash_host(const uint8_t* codes, uint32_t A, const uint8_t* blob, uint64_t blob_bytes,
-                     const uint64_t* obj_base, const uint32_t* attr_len, uint64_t n, uint64_t* coords,
-                     const HostRegions* R) {
-    HostSlot* slots;
-    hdx_status st = thread_slots(&slots);
-    if (st != HDX_OK) return st;
+struct PackedSource {
+    const uint8_t* codes;
+    uint32_t A;
+    const uint8_t* blob;
+    uint64_t blob_bytes;
+    const uint64_t* obj_base;
+    const uint32_t* attr_len;
+    const HostRegions* R;  // may be NULL
+    const bool blob_pinned = is_pinned(blob), len_pinned = is_pinned(attr_len);
+    const uint8_t* const blob_dev = blob_pinned ? device_view(blob) : nullptr;  // the gather kernel's view
     const int dev = thread_device();
+    std::vector<uint32_t> sizes;  // of the objects validated and not yet uploaded, in order
+
+    uint32_t stores() const { return 1; }
+    bool device_packs() const { return blob_dev != nullptr; }
 
     // Host-side validation (the reference asserts here) and the object's byte
-    // extent, done chunk by chunk as the pipeline below reaches each object, so
-    // the first copies start after one chunk's validation, not the batch's.
-    auto extent = [&](uint64_t i, uint64_t* out) -> hdx_status {
+    // extent, done chunk by chunk as the pipeline reaches each object, so the
+    // first copies start after one chunk's validation, not the batch's.
+    hdx_status object(uint64_t i, ObjectExtents& o) {
         uint64_t s = 0;
         for (uint32_t j = 0; j < A; ++j) {
             const uint32_t L = attr_len[i * A + j];
@@ -163,159 +231,109 @@ hdx_status hash_host(const uint8_t* codes, uint32_t A, const uint8_t* blob, uint
         if (obj_base[i] > blob_bytes || s > blob_bytes - obj_base[i])
             return fail(HDX_E_INVALID, "object %llu [%llu,+%llu) outside blob of %llu bytes", (unsigned long long)i,
                         (unsigned long long)obj_base[i], (unsigned long long)s, (unsigned long long)blob_bytes);
-        *out = s;
+        sizes.push_back((uint32_t)s);
+        o.count = 1;
+        o.ext[0] = {0, obj_base[i], s};
         return HDX_OK;
-    };
+    }
 
-    const bool blob_pinned = is_pinned(blob);
-    const bool len_pinned = is_pinned(attr_len);
-    Outputs out{A, coords, coords && is_pinned(coords), R, R && R->T && is_pinned(R->ids)};
-    const uint32_t T = out.T();
-
-    Pending pend[2];
-    auto finish = [&](int k) -> hdx_status {
-        if (!pend[k].live) return HDX_OK;
-        pend[k].live = false;
-        HIP_TRY(hipStreamSynchronize(slots[k].s));
-        out.land(slots[k], pend[k].first, pend[k].cnt);
-        return HDX_OK;
-    };
-    auto drain = [&](hdx_status err) {  // an error: let every copy in flight land before returning
-        for (int q = 0; q < 2; ++q) {
-            (void)finish(q);
-            (void)hipStreamSynchronize(slots[q].s);
-        }
-        return err;
-    };
-
-    const uint8_t* blob_dev = blob_pinned ? device_view(blob) : nullptr;  // the gather kernel's view
-    std::vector<uint32_t> sizes;  // the chunk's object sizes (validated as the chunk grows)
-    uint64_t i = 0, next_size = 0;
-    int k = 0;
-    if ((st = extent(0, &next_size)) != HDX_OK) return st;
-    while (i < n) {
-        // Grow the chunk while its payload stays under kChunkBytes (an object
-        // that does not fit starts the next chunk; its extent is kept), then
-        // move it as one span when its objects lie (nearly) back to back, else
-        // packed in index order.
-        uint64_t lo = obj_base[i], hi = obj_base[i] + next_size, payload = next_size, e = i + 1;
-        sizes.assign(1, (uint32_t)next_size);
-        uint64_t limit = i == 0 ? kFirstChunkBytes : kChunkBytes;
-        while (e < n) {
-            if ((st = extent(e, &next_size)) != HDX_OK) return drain(st);
-            if (payload + next_size > limit) {
-                // a chunk the device will pack grows further
-                if (limit == kChunkBytes && blob_dev && !span_pays(hi - lo, payload)) limit = kPackChunkBytes;
-                if (payload + next_size > limit) break;
-            }
-            lo = std::min(lo, obj_base[e]);
-            hi = std::max(hi, obj_base[e] + next_size);
-            payload += next_size;
-            sizes.push_back((uint32_t)next_size);
-            ++e;
-        }
-        const uint64_t cnt = e - i;
-        const bool span = cnt == 1 || span_pays(hi - lo, payload);  // one object: its own bytes, however large
-        const uint64_t bytes = span ? hi - lo : payload;
-        HostSlot& sl = slots[k];
-        if ((st = finish(k)) != HDX_OK) return drain(st);
-        if ((st = sl.d_blob.need(std::max<uint64_t>(bytes, 1))) != HDX_OK || (st = sl.d_base.need(cnt)) != HDX_OK ||
+    // The chunk as one span when its objects lie (nearly) back to back, else
+    // packed in index order.
+    hdx_status upload(HostSlot& sl, const Chunk& c) {
+        const uint64_t i = c.first, cnt = c.cnt, lo = c.lo[0], bytes = c.moved();
+        const uint32_t T = R ? R->T : 0;
+        hdx_status st;
+        if ((st = sl.d_blob.need(std::max<uint64_t>(bytes, 1))) != HDX_OK || (st = sl.d_off.need(cnt)) != HDX_OK ||
             (st = sl.d_len.need(cnt * A)) != HDX_OK || (st = sl.d_coords.need(cnt * A)) != HDX_OK ||
-            (T && (st = sl.d_ids.need(cnt * T)) != HDX_OK) || (st = sl.h_base.need(cnt)) != HDX_OK)
-            return drain(st);
-        const bool gather = !span && blob_dev;  // pinned objects out of order: packed on the device
-        const uint8_t* src_blob = blob + lo;
-        if (span) {
-            for (uint64_t t = 0; t < cnt; ++t) sl.h_base.p[t] = obj_base[i + t] - lo;
-            if (!blob_pinned) {
-                if ((st = sl.h_blob.need(std::max<uint64_t>(bytes, 1))) != HDX_OK) return drain(st);
-                std::memcpy(sl.h_blob.p, blob + lo, bytes);
-                src_blob = sl.h_blob.p;
-            }
+            (T && (st = sl.d_ids.need(cnt * T)) != HDX_OK) || (st = sl.h_off.need(cnt)) != HDX_OK)
+            return st;
+        const bool gather = !c.span && blob_dev;  // pinned objects out of order: packed on the device
+        const uint8_t* src_blob = nullptr;
+        if (c.span) {
+            for (uint64_t t = 0; t < cnt; ++t) sl.h_off.p[t] = obj_base[i + t] - lo;
+            if ((st = pinned_or_staged(blob + lo, blob_pinned, sl.h_blob, bytes, &src_blob)) != HDX_OK) return st;
         } else {
             uint64_t at = 0;  // packed offsets, index order
             for (uint64_t t = 0; t < cnt; ++t) {
-                sl.h_base.p[t] = at;
+                sl.h_off.p[t] = at;
                 at += sizes[t];
             }
             if (gather) {
                 if ((st = sl.h_src.need(cnt)) != HDX_OK || (st = sl.h_sz.need(cnt)) != HDX_OK ||
                     (st = sl.d_src.need(cnt)) != HDX_OK || (st = sl.d_sz.need(cnt)) != HDX_OK)
-                    return drain(st);
+                    return st;
                 std::memcpy(sl.h_src.p, obj_base + i, cnt * 8);
                 std::memcpy(sl.h_sz.p, sizes.data(), cnt * 4);
             } else {  // pageable: each object copied into the pinned staging
-                if ((st = sl.h_blob.need(std::max<uint64_t>(bytes, 1))) != HDX_OK) return drain(st);
-                for (uint64_t t = 0; t < cnt; ++t) std::memcpy(sl.h_blob.p + sl.h_base.p[t], blob + obj_base[i + t], sizes[t]);
+                if ((st = sl.h_blob.need(std::max<uint64_t>(bytes, 1))) != HDX_OK) return st;
+                for (uint64_t t = 0; t < cnt; ++t) std::memcpy(sl.h_blob.p + sl.h_off.p[t], blob + obj_base[i + t], sizes[t]);
                 src_blob = sl.h_blob.p;
             }
         }
-        const uint32_t* src_len = attr_len + i * A;
-        if (!len_pinned) {
-            if ((st = sl.h_len.need(cnt * A)) != HDX_OK) return drain(st);
-            std::memcpy(sl.h_len.p, attr_len + i * A, cnt * A * sizeof(uint32_t));
-            src_len = sl.h_len.p;
-        }
+        sizes.erase(sizes.begin(), sizes.begin() + cnt);  // at most the next chunk's first object stays
+        const uint32_t* src_len;
+        if ((st = pinned_or_staged(attr_len + i * A, len_pinned, sl.h_len, cnt * A, &src_len)) != HDX_OK) return st;
+        const SmallCopy off{sl.h_off.p, sl.d_off.p, cnt * 8}, len{src_len, sl.d_len.p, cnt * A * 4};
         if (gather) {
-            // every input of the chunk moved by the compute queue: the small
-            // arrays by one copy kernel (pinned staging or the caller's pinned
-            // lengths, through their device views), the objects by the gather
-            const void* lsrc[4] = {device_view((const uint8_t*)sl.h_base.p), device_view((const uint8_t*)sl.h_src.p),
-                                   device_view((const uint8_t*)sl.h_sz.p), device_view((const uint8_t*)src_len)};
-            void* ldst[4] = {sl.d_base.p, sl.d_src.p, sl.d_sz.p, sl.d_len.p};
-            const uint64_t lbytes[4] = {cnt * 8, cnt * 8, cnt * 4, cnt * A * 4};
-            if (lsrc[0] && lsrc[1] && lsrc[2] && lsrc[3]) {
-                DRAIN_TRY(launch_copy_linear(lsrc, ldst, lbytes, 4, sl.s));
-            } else {
-                DRAIN_TRY(hipMemcpyAsync(sl.d_base.p, sl.h_base.p, cnt * 8, hipMemcpyHostToDevice, sl.s));
-                DRAIN_TRY(hipMemcpyAsync(sl.d_src.p, sl.h_src.p, cnt * 8, hipMemcpyHostToDevice, sl.s));
-                DRAIN_TRY(hipMemcpyAsync(sl.d_sz.p, sl.h_sz.p, cnt * 4, hipMemcpyHostToDevice, sl.s));
-                DRAIN_TRY(hipMemcpyAsync(sl.d_len.p, src_len, cnt * A * 4, hipMemcpyHostToDevice, sl.s));
-            }
-            DRAIN_TRY(launch_gather_extents(blob_dev, sl.d_src.p, sl.d_sz.p, sl.d_base.p, sl.d_blob.p, cnt, sl.s));
+            const SmallCopy small[] = {off, {sl.h_src.p, sl.d_src.p, cnt * 8}, {sl.h_sz.p, sl.d_sz.p, cnt * 4}, len};
+            if ((st = copy_small(small, 4, true, sl.s)) != HDX_OK) return st;
+            HIP_TRY(launch_gather_extents(blob_dev, sl.d_src.p, sl.d_sz.p, sl.d_off.p, sl.d_blob.p, cnt, sl.s));
         } else {
-            DRAIN_TRY(hipMemcpyAsync(sl.d_base.p, sl.h_base.p, cnt * 8, hipMemcpyHostToDevice, sl.s));
-            DRAIN_TRY(hipMemcpyAsync(sl.d_len.p, src_len, cnt * A * 4, hipMemcpyHostToDevice, sl.s));
-            DRAIN_TRY(hipMemcpyAsync(sl.d_blob.p, src_blob, bytes, hipMemcpyHostToDevice, sl.s));
+            const SmallCopy small[] = {off, len};
+            if ((st = copy_small(small, 2, false, sl.s)) != HDX_OK) return st;
+            HIP_TRY(hipMemcpyAsync(sl.d_blob.p, src_blob, bytes, hipMemcpyHostToDevice, sl.s));
         }
+        return HDX_OK;
+    }
+
+    hdx_status launch(HostSlot& sl, const Chunk& c) {
+        const uint32_t T = R ? R->T : 0;
         BatchArgs args;
         // status: none (sizes validated above); the coordinates always land in
         // device staging, so the regions form needs no scratch of its own
-        if ((st = batch_args(args, codes, A, sl.d_blob.p, sl.d_base.p, sl.d_len.p, cnt, sl.d_coords.p, nullptr,
-                             R ? R->tables : nullptr, T, sl.d_ids.p, cnt, dev)) != HDX_OK)
-            return drain(st);
+        const hdx_status st = batch_args(args, codes, A, sl.d_blob.p, sl.d_off.p, sl.d_len.p, c.cnt, sl.d_coords.p,
+                                         nullptr, R ? R->tables : nullptr, T, sl.d_ids.p, c.cnt, dev);
+        if (st != HDX_OK) return st;
         if (T) {
-            const hipError_t e2 = launch_hash_batch_regions(args, sl.s);
-            if (e2 != hipSuccess) return drain(hip_fail(e2, "launch_hash_batch_regions"));
+            HIP_TRY(launch_hash_batch_regions(args, sl.s));
         } else {
-            const hipError_t e2 = launch_hash_batch(args, sl.s);
-            if (e2 != hipSuccess) return drain(hip_fail(e2, "launch_hash_batch"));
+            HIP_TRY(launch_hash_batch(args, sl.s));
         }
-        if ((st = out.copy_back(sl, i, cnt)) != HDX_OK) return drain(st);
-        pend[k] = {true, i, cnt};
-        i = e;
-        k ^= 1;
+        return HDX_OK;
     }
-    if ((st = finish(k)) != HDX_OK) return drain(st);
-    return finish(k ^ 1);
-}
+};
 
 // ---- stored objects (the reindex sweep from host memory) ----------------------------
 
-hdx_status hash_encoded_host(const uint8_t* codes, uint32_t A, const uint8_t* keys, uint64_t keys_bytes,
-                             const uint64_t* key_off, const uint32_t* key_len, const uint8_t* vals,
-                             uint64_t vals_bytes, const uint64_t* val_off, const uint32_t* val_len, uint64_t n,
-                             uint64_t* coords, uint64_t* versions, const HostRegions* R, uint32_t* status_bits) {
-    *status_bits = 0;
-    HostSlot* slots;
-    hdx_status st = thread_slots(&slots);
-    if (st != HDX_OK) return st;
-    const int dev = thread_device();
+struct StoredSource {
+    const uint8_t* codes;
+    uint32_t A;
+    const uint8_t* keys;
+    uint64_t keys_bytes;
+    const uint64_t* key_off;
+    const uint32_t* key_len;
+    const uint8_t* vals;
+    uint64_t vals_bytes;
+    const uint64_t* val_off;
+    const uint32_t* val_len;
+    const HostRegions* R;  // may be NULL
     // records [key][value] in one store (keys == vals, a LevelDB block's
     // adjacency): one span per chunk, and the kernel sees keys == vals
     const bool records = keys == vals;
+    const uint32_t vstore = records ? 0 : 1;  // the values' store (hdx_chunks.h)
+    const bool keys_pinned = is_pinned(keys), vals_pinned = is_pinned(vals);
+    const bool klen_pinned = is_pinned(key_len), vlen_pinned = is_pinned(val_len);
+    // keys and values out of order: packed as records [key][value] in index
+    // order (hdx_gather.hip from pinned stores, a host copy per object from
+    // pageable ones), so the kernel sees the record layout
+    const uint8_t* const keys_dev = keys_pinned ? device_view(keys) : nullptr;
+    const uint8_t* const vals_dev = vals_pinned ? device_view(vals) : nullptr;
+    const int dev = thread_device();
 
-    auto check = [&](uint64_t i) -> hdx_status {
+    uint32_t stores() const { return records ? 1 : 2; }
+    bool device_packs() const { return keys_dev && vals_dev; }
+
+    hdx_status object(uint64_t i, ObjectExtents& o) const {
         const uint32_t kl = key_len[i];
         if (is_numeric_code(codes[0]) && kl != 0 && kl != 8)
             return fail(HDX_E_BADSIZE, "object %llu: numeric key of %u bytes", (unsigned long long)i, kl);
@@ -326,208 +344,122 @@ hdx_status hash_encoded_host(const uint8_t* codes, uint32_t A, const uint8_t* ke
             return fail(HDX_E_INVALID, "object %llu: value [%llu,+%u) outside values of %llu bytes",
                         (unsigned long long)i, (unsigned long long)val_off[i], val_len[i],
                         (unsigned long long)vals_bytes);
+        o.count = 2;
+        o.ext[0] = {0, key_off[i], kl};
+        o.ext[1] = {vstore, val_off[i], val_len[i]};
         return HDX_OK;
-    };
+    }
 
-    const bool keys_pinned = is_pinned(keys), vals_pinned = is_pinned(vals);
-    const bool klen_pinned = is_pinned(key_len), vlen_pinned = is_pinned(val_len);
-    Outputs out{A, coords, coords && is_pinned(coords), R, R && R->T && is_pinned(R->ids)};
-    out.versions = versions;
-    out.versions_pinned = versions && is_pinned(versions);
-    const uint32_t T = out.T();
-
-    Pending pend[2];
-    auto finish = [&](int k) -> hdx_status {
-        if (!pend[k].live) return HDX_OK;
-        pend[k].live = false;
-        HIP_TRY(hipStreamSynchronize(slots[k].s));
-        out.land(slots[k], pend[k].first, pend[k].cnt);
-        *status_bits |= *slots[k].h_status.p;
-        return HDX_OK;
-    };
-    auto drain = [&](hdx_status err) {  // an error: let every copy in flight land before returning
-        for (int q = 0; q < 2; ++q) {
-            (void)finish(q);
-            (void)hipStreamSynchronize(slots[q].s);
-        }
-        return err;
-    };
-    // a span's host source: the caller's pinned bytes, or a pinned copy
-    auto stage = [&](PinBuf<uint8_t>& buf, const uint8_t* base, bool pinned, uint64_t lo, uint64_t bytes,
-                     const uint8_t** src) -> hdx_status {
-        if (pinned) {
-            *src = base + lo;
-            return HDX_OK;
-        }
-        hdx_status s2 = buf.need(std::max<uint64_t>(bytes, 1));
-        if (s2 != HDX_OK) return s2;
-        std::memcpy(buf.p, base + lo, bytes);
-        *src = buf.p;
-        return HDX_OK;
-    };
-
-    // keys and values out of order: packed as records [key][value] in index
-    // order (hdx_gather.hip from pinned stores, a host copy per object from
-    // pageable ones), so the kernel sees the record layout
-    const uint8_t* keys_dev = keys_pinned ? device_view(keys) : nullptr;
-    const uint8_t* vals_dev = vals_pinned ? device_view(vals) : nullptr;
-    uint64_t i = 0;
-    int k = 0;
-    if ((st = check(0)) != HDX_OK) return st;
-    while (i < n) {
-        uint64_t klo = key_off[i], khi = key_off[i] + key_len[i];
-        uint64_t vlo = val_off[i], vhi = val_off[i] + val_len[i];
-        uint64_t payload = (uint64_t)key_len[i] + val_len[i];
-        if (records) {
-            klo = vlo = std::min(klo, vlo);
-            khi = vhi = std::max(khi, vhi);
-        }
-        auto span_bytes = [&](uint64_t a, uint64_t b, uint64_t c, uint64_t d) {
-            return records ? d - c : (b - a) + (d - c);
-        };
-        uint64_t e = i + 1;
-        uint64_t limit = i == 0 ? kFirstChunkBytes : kChunkBytes;
-        while (e < n) {
-            if ((st = check(e)) != HDX_OK) return drain(st);
-            const uint64_t pe = (uint64_t)key_len[e] + val_len[e];
-            if (payload + pe > limit) {
-                if (limit == kChunkBytes && keys_dev && vals_dev && !span_pays(span_bytes(klo, khi, vlo, vhi), payload))
-                    limit = kPackChunkBytes;  // packed on the device: larger chunks
-                if (payload + pe > limit) break;
-            }
-            uint64_t nklo = std::min(klo, key_off[e]), nkhi = std::max(khi, key_off[e] + key_len[e]);
-            uint64_t nvlo = std::min(vlo, val_off[e]), nvhi = std::max(vhi, val_off[e] + val_len[e]);
-            if (records) {
-                nklo = nvlo = std::min(nklo, nvlo);
-                nkhi = nvhi = std::max(nkhi, nvhi);
-            }
-            klo = nklo; khi = nkhi; vlo = nvlo; vhi = nvhi;
-            payload += pe;
-            ++e;
-        }
-        const uint64_t cnt = e - i;
-        // one object whose spans hold nothing else moves as spans, however large
-        const bool span = span_pays(span_bytes(klo, khi, vlo, vhi), payload) ||
-                          (cnt == 1 && span_bytes(klo, khi, vlo, vhi) == payload);
-        const bool gather = !span && keys_dev && vals_dev;
-        const bool packed = !span;  // the chunk's device layout is then records
-        HostSlot& sl = slots[k];
-        if ((st = finish(k)) != HDX_OK) return drain(st);
-        if ((st = sl.d_blob.need(std::max<uint64_t>(span ? vhi - vlo : payload, 1))) != HDX_OK ||
-            (span && !records && (st = sl.d_keys.need(std::max<uint64_t>(khi - klo, 1))) != HDX_OK) ||
-            (st = sl.d_koff.need(cnt)) != HDX_OK || (st = sl.d_voff.need(cnt)) != HDX_OK ||
-            (st = sl.d_klen.need(cnt)) != HDX_OK || (st = sl.d_vlen.need(cnt)) != HDX_OK ||
+    hdx_status upload(HostSlot& sl, const Chunk& c) {
+        const uint64_t i = c.first, cnt = c.cnt, bytes = c.span ? c.hi[vstore] - c.lo[vstore] : c.payload;
+        const uint64_t klo = c.lo[0], vlo = c.lo[vstore], key_bytes = c.hi[0] - klo;
+        const uint32_t T = R ? R->T : 0;
+        const bool key_span = c.span && !records;  // the key column's span beside the values'
+        const bool gather = !c.span && device_packs();
+        hdx_status st;
+        if ((st = sl.d_blob.need(std::max<uint64_t>(bytes, 1))) != HDX_OK ||
+            (key_span && (st = sl.d_keys.need(std::max<uint64_t>(key_bytes, 1))) != HDX_OK) ||
+            (st = sl.d_off.need(cnt)) != HDX_OK || (st = sl.d_voff.need(cnt)) != HDX_OK ||
+            (st = sl.d_len.need(cnt)) != HDX_OK || (st = sl.d_vlen.need(cnt)) != HDX_OK ||
             (st = sl.d_coords.need(cnt * A)) != HDX_OK || (st = sl.d_ver.need(cnt)) != HDX_OK ||
             (st = sl.d_status.need(1)) != HDX_OK || (st = sl.h_status.need(1)) != HDX_OK ||
-            (T && (st = sl.d_ids.need(cnt * T)) != HDX_OK) || (st = sl.h_koff.need(cnt)) != HDX_OK ||
+            (T && (st = sl.d_ids.need(cnt * T)) != HDX_OK) || (st = sl.h_off.need(cnt)) != HDX_OK ||
             (st = sl.h_voff.need(cnt)) != HDX_OK)
-            return drain(st);
+            return st;
         const uint8_t *src_vals = nullptr, *src_keys = nullptr;
-        if (span) {
+        if (c.span) {
             for (uint64_t t = 0; t < cnt; ++t) {
-                sl.h_koff.p[t] = key_off[i + t] - klo;
+                sl.h_off.p[t] = key_off[i + t] - klo;
                 sl.h_voff.p[t] = val_off[i + t] - vlo;
             }
-            if ((st = stage(sl.h_blob, vals, vals_pinned, vlo, vhi - vlo, &src_vals)) != HDX_OK) return drain(st);
-            if (!records && (st = stage(sl.h_keys, keys, keys_pinned, klo, khi - klo, &src_keys)) != HDX_OK)
-                return drain(st);
+            if ((st = pinned_or_staged(vals + vlo, vals_pinned, sl.h_blob, bytes, &src_vals)) != HDX_OK) return st;
+            if (key_span && (st = pinned_or_staged(keys + klo, keys_pinned, sl.h_keys, key_bytes, &src_keys)) != HDX_OK)
+                return st;
         } else {
-            uint64_t at = 0;  // record t: its key at h_koff, its value right after
+            uint64_t at = 0;  // record t: its key at h_off, its value right after
             for (uint64_t t = 0; t < cnt; ++t) {
-                sl.h_koff.p[t] = at;
+                sl.h_off.p[t] = at;
                 sl.h_voff.p[t] = at + key_len[i + t];
                 at += (uint64_t)key_len[i + t] + val_len[i + t];
             }
             if (gather) {  // 2 extents per object, absolute device-view sources
                 if ((st = sl.h_src.need(2 * cnt)) != HDX_OK || (st = sl.h_sz.need(2 * cnt)) != HDX_OK ||
-                    (st = sl.h_src2.need(2 * cnt)) != HDX_OK || (st = sl.d_src.need(2 * cnt)) != HDX_OK ||
-                    (st = sl.d_sz.need(2 * cnt)) != HDX_OK || (st = sl.d_src2.need(2 * cnt)) != HDX_OK)
-                    return drain(st);
+                    (st = sl.h_dst.need(2 * cnt)) != HDX_OK || (st = sl.d_src.need(2 * cnt)) != HDX_OK ||
+                    (st = sl.d_sz.need(2 * cnt)) != HDX_OK || (st = sl.d_dst.need(2 * cnt)) != HDX_OK)
+                    return st;
                 for (uint64_t t = 0; t < cnt; ++t) {
                     sl.h_src.p[2 * t] = (uint64_t)(uintptr_t)keys_dev + key_off[i + t];
                     sl.h_sz.p[2 * t] = key_len[i + t];
-                    sl.h_src2.p[2 * t] = sl.h_koff.p[t];
+                    sl.h_dst.p[2 * t] = sl.h_off.p[t];
                     sl.h_src.p[2 * t + 1] = (uint64_t)(uintptr_t)vals_dev + val_off[i + t];
                     sl.h_sz.p[2 * t + 1] = val_len[i + t];
-                    sl.h_src2.p[2 * t + 1] = sl.h_voff.p[t];
+                    sl.h_dst.p[2 * t + 1] = sl.h_voff.p[t];
                 }
             } else {  // pageable: each key and value copied into the pinned staging
-                if ((st = sl.h_blob.need(std::max<uint64_t>(payload, 1))) != HDX_OK) return drain(st);
+                if ((st = sl.h_blob.need(std::max<uint64_t>(bytes, 1))) != HDX_OK) return st;
                 for (uint64_t t = 0; t < cnt; ++t) {
-                    std::memcpy(sl.h_blob.p + sl.h_koff.p[t], keys + key_off[i + t], key_len[i + t]);
+                    std::memcpy(sl.h_blob.p + sl.h_off.p[t], keys + key_off[i + t], key_len[i + t]);
                     std::memcpy(sl.h_blob.p + sl.h_voff.p[t], vals + val_off[i + t], val_len[i + t]);
                 }
                 src_vals = sl.h_blob.p;
             }
         }
-        const uint32_t* src_klen = key_len + i;
-        const uint32_t* src_vlen = val_len + i;
-        if (!klen_pinned) {
-            if ((st = sl.h_klen.need(cnt)) != HDX_OK) return drain(st);
-            std::memcpy(sl.h_klen.p, key_len + i, cnt * 4);
-            src_klen = sl.h_klen.p;
-        }
-        if (!vlen_pinned) {
-            if ((st = sl.h_vlen.need(cnt)) != HDX_OK) return drain(st);
-            std::memcpy(sl.h_vlen.p, val_len + i, cnt * 4);
-            src_vlen = sl.h_vlen.p;
-        }
-        const void* lsrc[7] = {device_view((const uint8_t*)sl.h_koff.p), device_view((const uint8_t*)sl.h_voff.p),
-                               device_view((const uint8_t*)src_klen), device_view((const uint8_t*)src_vlen),
-                               gather ? device_view((const uint8_t*)sl.h_src.p) : nullptr,
-                               gather ? device_view((const uint8_t*)sl.h_sz.p) : nullptr,
-                               gather ? device_view((const uint8_t*)sl.h_src2.p) : nullptr};
-        if (gather && lsrc[0] && lsrc[1] && lsrc[2] && lsrc[3] && lsrc[4] && lsrc[5] && lsrc[6]) {
-            // every input of the chunk moved by the compute queue (one copy
-            // kernel, then the gather): no SDMA copy for the gather to wait on
-            void* ldst[7] = {sl.d_koff.p, sl.d_voff.p, sl.d_klen.p, sl.d_vlen.p, sl.d_src.p, sl.d_sz.p, sl.d_src2.p};
-            const uint64_t lbytes[7] = {cnt * 8, cnt * 8, cnt * 4, cnt * 4, 2 * cnt * 8, 2 * cnt * 4, 2 * cnt * 8};
-            DRAIN_TRY(launch_copy_linear(lsrc, ldst, lbytes, 7, sl.s));
-        } else {
-            DRAIN_TRY(hipMemcpyAsync(sl.d_koff.p, sl.h_koff.p, cnt * 8, hipMemcpyHostToDevice, sl.s));
-            DRAIN_TRY(hipMemcpyAsync(sl.d_voff.p, sl.h_voff.p, cnt * 8, hipMemcpyHostToDevice, sl.s));
-            DRAIN_TRY(hipMemcpyAsync(sl.d_klen.p, src_klen, cnt * 4, hipMemcpyHostToDevice, sl.s));
-            DRAIN_TRY(hipMemcpyAsync(sl.d_vlen.p, src_vlen, cnt * 4, hipMemcpyHostToDevice, sl.s));
-            if (gather) {
-                DRAIN_TRY(hipMemcpyAsync(sl.d_src.p, sl.h_src.p, 2 * cnt * 8, hipMemcpyHostToDevice, sl.s));
-                DRAIN_TRY(hipMemcpyAsync(sl.d_sz.p, sl.h_sz.p, 2 * cnt * 4, hipMemcpyHostToDevice, sl.s));
-                DRAIN_TRY(hipMemcpyAsync(sl.d_src2.p, sl.h_src2.p, 2 * cnt * 8, hipMemcpyHostToDevice, sl.s));
-            }
-        }
+        const uint32_t *src_klen, *src_vlen;
+        if ((st = pinned_or_staged(key_len + i, klen_pinned, sl.h_len, cnt, &src_klen)) != HDX_OK ||
+            (st = pinned_or_staged(val_len + i, vlen_pinned, sl.h_vlen, cnt, &src_vlen)) != HDX_OK)
+            return st;
+        const SmallCopy small[] = {{sl.h_off.p, sl.d_off.p, cnt * 8},          {sl.h_voff.p, sl.d_voff.p, cnt * 8},
+                                   {src_klen, sl.d_len.p, cnt * 4},            {src_vlen, sl.d_vlen.p, cnt * 4},
+                                   {sl.h_src.p, sl.d_src.p, 2 * cnt * 8},      {sl.h_sz.p, sl.d_sz.p, 2 * cnt * 4},
+                                   {sl.h_dst.p, sl.d_dst.p, 2 * cnt * 8}};  // the last three: a gather's extents
+        if ((st = copy_small(small, gather ? 7 : 4, gather, sl.s)) != HDX_OK) return st;
         if (gather) {
-            DRAIN_TRY(launch_gather_extents(nullptr, sl.d_src.p, sl.d_sz.p, sl.d_src2.p, sl.d_blob.p, 2 * cnt, sl.s));
+            HIP_TRY(launch_gather_extents(nullptr, sl.d_src.p, sl.d_sz.p, sl.d_dst.p, sl.d_blob.p, 2 * cnt, sl.s));
         } else {
-            DRAIN_TRY(hipMemcpyAsync(sl.d_blob.p, src_vals, span ? vhi - vlo : payload, hipMemcpyHostToDevice, sl.s));
-            if (span && !records)
-                DRAIN_TRY(hipMemcpyAsync(sl.d_keys.p, src_keys, khi - klo, hipMemcpyHostToDevice, sl.s));
+            HIP_TRY(hipMemcpyAsync(sl.d_blob.p, src_vals, bytes, hipMemcpyHostToDevice, sl.s));
+            if (key_span) HIP_TRY(hipMemcpyAsync(sl.d_keys.p, src_keys, key_bytes, hipMemcpyHostToDevice, sl.s));
         }
-        DRAIN_TRY(hipMemsetAsync(sl.d_status.p, 0, 4, sl.s));
-        EncodedArgs a{};
-        if ((st = set_codes(a, codes, A)) != HDX_OK) return drain(st);
-        a.keys = records || packed ? sl.d_blob.p : sl.d_keys.p;
-        a.key_off = sl.d_koff.p;
-        a.key_len = sl.d_klen.p;
-        a.vals = sl.d_blob.p;
-        a.val_off = sl.d_voff.p;
-        a.val_len = sl.d_vlen.p;
-        a.coords = sl.d_coords.p;  // always staged: no scratch for the regions form
-        a.versions = sl.d_ver.p;
-        a.status = sl.d_status.p;
-        a.n = cnt;
-        a.A = A;
-        a.T = T;
-        for (uint32_t t = 0; t < T; ++t)
-            if ((st = fill_sweep_table(a.t[t], R->tables[t], dev, sl.d_ids.p + t * cnt)) != HDX_OK) return drain(st);
-        const hipError_t e2 = launch_hash_encoded(a, sl.s);
-        if (e2 != hipSuccess) return drain(hip_fail(e2, "launch_hash_encoded"));
-        if ((st = out.copy_back(sl, i, cnt)) != HDX_OK) return drain(st);
-        DRAIN_TRY(hipMemcpyAsync(sl.h_status.p, sl.d_status.p, 4, hipMemcpyDeviceToHost, sl.s));
-        pend[k] = {true, i, cnt};
-        i = e;
-        k ^= 1;
+        return HDX_OK;
     }
-    if ((st = finish(k)) != HDX_OK) return drain(st);
-    return finish(k ^ 1);
+
+    hdx_status launch(HostSlot& sl, const Chunk& c) {
+        HIP_TRY(hipMemsetAsync(sl.d_status.p, 0, 4, sl.s));
+        // a packed chunk's device layout is records; the coordinates are
+        // always staged, so the regions form needs no scratch
+        const uint8_t* d_keys = records || !c.span ? sl.d_blob.p : sl.d_keys.p;
+        EncodedArgs a;
+        const hdx_status st =
+            encoded_args(a, codes, A, d_keys, sl.d_off.p, sl.d_len.p, sl.d_blob.p, sl.d_voff.p, sl.d_vlen.p, c.cnt,
+                         sl.d_coords.p, sl.d_ver.p, sl.d_status.p, R ? R->tables : nullptr, R ? R->T : 0, sl.d_ids.p,
+                         c.cnt, dev);
+        if (st != HDX_OK) return st;
+        HIP_TRY(launch_hash_encoded(a, sl.s));
+        return HDX_OK;
+    }
+};
+
+}  // namespace
+
+hdx_status hash_host(const uint8_t* codes, uint32_t A, const uint8_t* blob, uint64_t blob_bytes,
+                     const uint64_t* obj_base, const uint32_t* attr_len, uint64_t n, uint64_t* coords,
+                     const HostRegions* R) {
+    HostSlot* slots;
+    const hdx_status st = thread_slots(&slots);
+    if (st != HDX_OK) return st;
+    PackedSource src{codes, A, blob, blob_bytes, obj_base, attr_len, R};
+    return run_chunks(slots, src, n, Outputs(A, coords, R), nullptr);
+}
+
+hdx_status hash_encoded_host(const uint8_t* codes, uint32_t A, const uint8_t* keys, uint64_t keys_bytes,
+                             const uint64_t* key_off, const uint32_t* key_len, const uint8_t* vals,
+                             uint64_t vals_bytes, const uint64_t* val_off, const uint32_t* val_len, uint64_t n,
+                             uint64_t* coords, uint64_t* versions, const HostRegions* R, uint32_t* status_bits) {
+    *status_bits = 0;
+    HostSlot* slots;
+    const hdx_status st = thread_slots(&slots);
+    if (st != HDX_OK) return st;
+    StoredSource src{codes, A, keys, keys_bytes, key_off, key_len, vals, vals_bytes, val_off, val_len, R};
+    return run_chunks(slots, src, n, Outputs(A, coords, R, versions), status_bits);
 }
 
 }  // namespace hdx

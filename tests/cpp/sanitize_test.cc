@@ -14,7 +14,10 @@
 //     which rows) applied to per-device matrices holding only their own
 //     rows, for equal, unequal and empty shards at world 1..8, coordinates
 //     and region-id sections: every device must end with the full matrix;
-//   * the cut rule over stored objects (key + value bytes, the host sweep).
+//   * the cut rule over stored objects (key + value bytes, the host sweep);
+//   * the host pipelines' chunk planner (hdx_chunks.h) on layouts whose chunk
+//     lists follow from its rules by hand: ordered, gapped, at the span
+//     threshold, a giant object, two stores, empty objects, a rejected object.
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -25,6 +28,7 @@
 #include <random>
 #include <vector>
 
+#include "hdx_chunks.h"
 #include "hdx_cuts.h"
 #include "hdx_exchange.h"
 #include "hdx_host_common.h"
@@ -61,6 +65,155 @@ struct Exact {
 };
 
 static const uint32_t kTypes[] = {9217, 9218, 9219, 9473, 9474, 9475, 9476, 9477, 9478, 9223, 9281, 9417};
+
+// ---- the host pipelines' chunk planner (hdx_chunks.h) ----------------------------
+// A source over plain arrays (no backing bytes: the planner reads none).  An
+// object is a value extent, after a key extent when there are keys; `stores`
+// 1 with keys: records.  Object `reject` fails validation.
+struct PlanSource {
+    std::vector<uint64_t> koff, klen, voff, vlen;
+    uint32_t nstores = 1;
+    uint64_t reject = UINT64_MAX;
+    std::vector<uint32_t> seen;  // validations per object: each exactly once
+
+    uint64_t n() const { return voff.size(); }
+    uint32_t stores() const { return nstores; }
+    hdx_status object(uint64_t i, hdx::ObjectExtents& o) {
+        seen.resize(n());
+        ++seen[i];
+        if (i == reject) return HDX_E_BADSIZE;
+        o.count = 0;
+        if (!koff.empty()) o.ext[o.count++] = {0, koff[i], klen[i]};
+        o.ext[o.count++] = {nstores - 1, voff[i], vlen[i]};
+        return HDX_OK;
+    }
+    // n values of `size` bytes, object i at i * stride
+    static PlanSource values(uint64_t n, uint64_t size, uint64_t stride) {
+        PlanSource s;
+        for (uint64_t i = 0; i < n; ++i) {
+            s.voff.push_back(i * stride);
+            s.vlen.push_back(size);
+        }
+        return s;
+    }
+};
+
+struct PlanWant {
+    uint64_t first, cnt;
+    bool span;
+    uint64_t moved;
+};
+
+// Plans the whole call; the chunk list must be `want` exactly and planning
+// must end with `end` (HDX_OK: after the last object).
+static std::vector<hdx::Chunk> plan_is(const char* what, PlanSource src, bool device_packs,
+                                       const std::vector<PlanWant>& want, hdx_status end = HDX_OK) {
+    std::vector<hdx::Chunk> got;
+    hdx::ChunkCursor cur;
+    hdx::Chunk c;
+    hdx_status st;
+    while ((st = hdx::next_chunk(src, src.n(), device_packs, cur, c)) == HDX_OK && c.cnt) got.push_back(c);
+    CHECK(st == end, "%s (packs %d): planning ended with %d, want %d", what, device_packs, (int)st, (int)end);
+    CHECK(got.size() == want.size(), "%s (packs %d): %zu chunks, want %zu", what, device_packs, got.size(),
+          want.size());
+    for (size_t k = 0; k < got.size() && k < want.size(); ++k)
+        CHECK(got[k].first == want[k].first && got[k].cnt == want[k].cnt && got[k].span == want[k].span &&
+                  got[k].moved() == want[k].moved,
+              "%s (packs %d) chunk %zu: (%llu,%llu) %s of %llu bytes, want (%llu,%llu) %s of %llu", what, device_packs,
+              k, (unsigned long long)got[k].first, (unsigned long long)got[k].cnt, got[k].span ? "span" : "packed",
+              (unsigned long long)got[k].moved(), (unsigned long long)want[k].first, (unsigned long long)want[k].cnt,
+              want[k].span ? "span" : "packed", (unsigned long long)want[k].moved);
+    const uint64_t upto = st == HDX_OK ? src.n() : src.reject + 1;  // every object reached was validated once
+    for (uint64_t i = 0; i < src.seen.size(); ++i)
+        CHECK(src.seen[i] == (i < upto ? 1u : 0u), "%s (packs %d): object %llu validated %u times", what, device_packs,
+              (unsigned long long)i, src.seen[i]);
+    return got;
+}
+
+static void planner_cases() {
+    const uint64_t KiB = 1ull << 10, MiB = 1ull << 20;
+    const bool S = true, P = false;  // span, packed
+    for (const bool packs : {true, false}) {
+        // 1. ordered: 300 objects of 1 MiB back to back
+        plan_is("ordered", PlanSource::values(300, MiB, MiB), packs,
+                {{0, 16, S, 16 * MiB}, {16, 128, S, 128 * MiB}, {144, 128, S, 128 * MiB}, {272, 28, S, 28 * MiB}});
+        // 4. a giant object among small ones, back to back
+        PlanSource giant;
+        uint64_t at = 0;
+        for (const uint64_t size : {KiB, KiB, 600 * MiB, KiB, KiB}) {
+            giant.voff.push_back(at);
+            giant.vlen.push_back(size);
+            at += size;
+        }
+        plan_is("giant", giant, packs, {{0, 2, S, 2 * KiB}, {2, 1, S, 600 * MiB}, {3, 2, S, 2 * KiB}});
+        // 8. validation: object 20 of case 1 rejected while the second chunk grows
+        PlanSource bad = PlanSource::values(300, MiB, MiB);
+        bad.reject = 20;
+        plan_is("rejected", bad, packs, {{0, 16, S, 16 * MiB}}, HDX_E_BADSIZE);
+    }
+    // 2. gapped: 700 objects of 1 MiB, object i at 2 i MiB
+    plan_is("gapped", PlanSource::values(700, MiB, 2 * MiB), true,
+            {{0, 16, P, 16 * MiB}, {16, 512, P, 512 * MiB}, {528, 172, P, 172 * MiB}});
+    plan_is("gapped", PlanSource::values(700, MiB, 2 * MiB), false,
+            {{0, 16, P, 16 * MiB},
+             {16, 128, P, 128 * MiB},
+             {144, 128, P, 128 * MiB},
+             {272, 128, P, 128 * MiB},
+             {400, 128, P, 128 * MiB},
+             {528, 128, P, 128 * MiB},
+             {656, 44, P, 44 * MiB}});
+    // 3. the span threshold: 8 objects of 1 MiB back to back, a gap G before the last
+    for (const uint64_t over : {0, 1}) {
+        const uint64_t G = MiB + 64 * KiB + over;
+        PlanSource s = PlanSource::values(8, MiB, MiB);
+        s.voff[7] += G;
+        if (over)
+            plan_is("threshold + 1", s, true, {{0, 8, P, 8 * MiB}});
+        else
+            plan_is("threshold", s, true, {{0, 8, S, 8 * MiB + G}});
+    }
+    // 5. two stores: 8-byte keys back to back in one, 1 MiB values back to back in the other
+    {
+        PlanSource s = PlanSource::values(300, MiB, MiB);
+        s.nstores = 2;
+        for (uint64_t i = 0; i < 300; ++i) {
+            s.koff.push_back(8 * i);
+            s.klen.push_back(8);
+        }
+        const std::vector<hdx::Chunk> got =
+            plan_is("two stores", s, true,
+                    {{0, 15, S, 15 * (MiB + 8)}, {15, 127, S, 127 * (MiB + 8)}, {142, 127, S, 127 * (MiB + 8)},
+                     {269, 31, S, 31 * (MiB + 8)}});
+        for (const hdx::Chunk& c : got) {
+            CHECK(c.payload == c.cnt * (MiB + 8), "two stores: payload %llu", (unsigned long long)c.payload);
+            CHECK(c.lo[0] == c.first * 8 && c.hi[0] - c.lo[0] == c.cnt * 8, "two stores: chunk at %llu moves keys [%llu,%llu)",
+                  (unsigned long long)c.first, (unsigned long long)c.lo[0], (unsigned long long)c.hi[0]);
+            CHECK(c.lo[1] == c.first * MiB && c.hi[1] - c.lo[1] == c.cnt * MiB,
+                  "two stores: chunk at %llu moves values [%llu,%llu)", (unsigned long long)c.first,
+                  (unsigned long long)c.lo[1], (unsigned long long)c.hi[1]);
+        }
+    }
+    // 6. one object, its key at [0, 8) and its value at [10 MiB, 11 MiB)
+    for (const uint32_t nstores : {1u, 2u}) {
+        PlanSource s;
+        s.nstores = nstores;
+        s.koff = {0};
+        s.klen = {8};
+        s.voff = {10 * MiB};
+        s.vlen = {MiB};
+        if (nstores == 1) {  // records: the span holds other bytes
+            plan_is("apart, one store", s, true, {{0, 1, P, MiB + 8}});
+        } else {
+            const std::vector<hdx::Chunk> got = plan_is("apart, two stores", s, true, {{0, 1, S, MiB + 8}});
+            CHECK(got.size() == 1 && got[0].hi[0] - got[0].lo[0] == 8 && got[0].lo[1] == 10 * MiB &&
+                      got[0].hi[1] == 11 * MiB,
+                  "apart, two stores: spans");
+        }
+    }
+    // 7. empty objects
+    plan_is("empty", PlanSource::values(3, 0, 0), true, {{0, 3, S, 0}});
+    plan_is("no objects", PlanSource::values(0, 0, 0), true, {});
+}
 
 int main() {
     std::mt19937_64 g(0x4859504552444558ull);
@@ -286,6 +439,7 @@ int main() {
             CHECK(first[k] == want[k], "stored cuts rep %d k %u: %llu vs %llu", rep, k, (unsigned long long)first[k],
                   (unsigned long long)want[k]);
     }
+    planner_cases();
     if (failures) {
         fprintf(stderr, "%d failures\n", failures);
         return 1;

@@ -122,6 +122,74 @@ def _pinned_np(a):
     return view, lambda: lib.hdx_free_pinned(p)
 
 
+_PIN_CASES = [(kind, blob, lens, coords) for kind in ("span", "packed") for blob in (False, True)
+              for lens in (False, True) for coords in (False, True)]
+_PIN_CASES += [("stored", store, lens, False) for store in ("keys", "vals") for lens in (False, True)]
+_pin_inputs = {}  # kind -> the shuffled inputs and the oracle's outputs, made once
+
+
+def _pin_case_inputs(oracle, kind):
+    if kind not in _pin_inputs:
+        types, blob, base, lens = synth.make_batch_host("cfg3b", 97, seed=53)
+        rng = np.random.default_rng(29)
+        if kind != "stored":  # gaps of ~2 % of the payload: a span; of ~190 %: packed
+            sblob, sbase = _shuffle(blob, base, lens, len(types), rng, max_gap=37 if kind == "span" else 4000)
+            _pin_inputs[kind] = (types, [sblob, sbase, lens], oracle.hash_batch(types, blob, base, lens)[0])
+        else:
+            keys, key_off, key_len, vals, val_off, val_len = synth.encode_store_host(types, blob, base, lens,
+                                                                                      first_version=11, layout="keycol")
+            skeys, nkoff = _scatter(keys, key_off, key_len, rng, 200)
+            svals, nvoff = _scatter(vals, val_off, val_len, rng, 3000)
+            enc = [skeys, nkoff, key_len, svals, nvoff, val_len]
+            want, wver, bad = oracle.hash_encoded(types, *enc)
+            assert not bad.any()
+            _pin_inputs[kind] = (types, enc, (want, wver))
+    return _pin_inputs[kind]
+
+
+@pytest.mark.parametrize("kind,main,lens,coords", _PIN_CASES,
+                         ids=["%s-%s-lens%d-coords%d" % (k, m if k == "stored" else "blob%d" % m, l, c)
+                              for k, m, l, c in _PIN_CASES])
+def test_each_array_pinned_or_pageable(oracle, kind, main, lens, coords):
+    """Which of a call's arrays are pinned, one by one (97 shuffled objects, one
+    chunk): every input goes from the caller's pinned array or through pinned
+    staging, every output lands in place or through staging.  A packed batch,
+    as one span and as a packed chunk (on the device from a pinned blob, by the
+    host from a pageable one): the blob, the lengths, the coordinates.  Stored
+    objects (a key column, wide gaps: a packed chunk): the keys pinned
+    and the values pageable, or the reverse — one pageable store and the host
+    packs the chunk — and both length arrays; versions requested."""
+    types, arrays, want = _pin_case_inputs(oracle, kind)
+    arrays = list(arrays)
+    closers = []
+
+    def pin(a):
+        view, close = _pinned_np(a)
+        closers.append(close)
+        return view
+
+    try:
+        if kind != "stored":
+            if main:
+                arrays[0] = pin(arrays[0])
+            if lens:
+                arrays[2] = pin(arrays[2])
+            out = np.zeros(want.size, np.uint64)
+            out = (pin(out) if coords else out).reshape(want.shape)
+            got = hdx.hash_batch_host(types, *arrays, out=out)
+            assert got is out and np.array_equal(got, want)
+        else:
+            store = 0 if main == "keys" else 3
+            arrays[store] = pin(arrays[store])
+            if lens:
+                arrays[2], arrays[5] = pin(arrays[2]), pin(arrays[5])
+            got, vers = hdx.hash_encoded_host(types, *arrays, versions=True)
+            assert np.array_equal(got, want[0]) and np.array_equal(vers, want[1])
+    finally:
+        for c in closers:
+            c()
+
+
 @pytest.mark.parametrize("pinned", [True, False])
 @pytest.mark.parametrize("records", [False, True])
 def test_shuffled_stores(oracle, pinned, records):

@@ -3,7 +3,8 @@
 
 tests/cpp/sanitize_test.cc links the per-object C-ABI (hyperdex_amd/csrc/hdx_cpu.cpp)
 and the device set's cut rule (hdx_cuts.h) with the oracle as the checker, every
-value in a heap buffer of exactly its length; built here with g++ (no GPU)."""
+value in a heap buffer of exactly its length, and the host pipelines' chunk
+planner (hdx_chunks.h) on hand-worked layouts; built here with g++ (no GPU)."""
 import os
 import shutil
 import subprocess
