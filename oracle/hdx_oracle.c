@@ -419,35 +419,46 @@ static uint32_t be32(const uint8_t* p) {
     return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3];
 }
 
+/* One stored value: 0 and *version, off[k] / len[k] (k < A - 1, offsets from
+ * the value's start) when it decodes, else 1.  :174-181 version, :185-192
+ * count, :198-213 the attributes.  Unlike the reference, the count must be the
+ * schema's A - 1 value attributes and every attribute must end inside the
+ * value (the reference checks neither). */
+int hdxo_decode_value(const uint8_t* v, uint32_t len, uint32_t A, uint64_t* version, uint64_t* off,
+                      uint32_t* n) {
+    const uint8_t* end = v + len;
+    const uint8_t* ptr = v;
+    if (ptr + 8 > end) return 1;
+    *version = be64(ptr);
+    ptr += 8;
+    if (ptr + 2 > end) return 1;
+    const uint32_t count = ((uint32_t)ptr[0] << 8) | ptr[1];
+    ptr += 2;
+    if (count != A - 1) return 1;
+    for (uint32_t k = 0; k < count; ++k) {
+        if (ptr + 4 > end) return 1;
+        n[k] = be32(ptr);
+        ptr += 4;
+        if ((uint64_t)(end - ptr) < n[k]) return 1;
+        off[k] = (uint64_t)(ptr - v);
+        ptr += n[k];
+    }
+    return 0;
+}
+
 int64_t hdxo_hash_encoded(const uint32_t* types, uint32_t A, const uint8_t* keys,
                           const uint64_t* key_off, const uint32_t* key_len, const uint8_t* vals,
                           const uint64_t* val_off, const uint32_t* val_len, uint64_t n,
                           uint64_t* coords, uint64_t* versions, uint8_t* bad) {
     int64_t nbad = 0;
     /* any schema width (the reference's attrs_sz is a u16, common/schema.h:49) */
-    const uint8_t** attr_p = (const uint8_t**)malloc(sizeof(*attr_p) * (A ? A : 1));
+    uint64_t* attr_o = (uint64_t*)malloc(sizeof(*attr_o) * (A ? A : 1));
     uint32_t* attr_n = (uint32_t*)malloc(sizeof(*attr_n) * (A ? A : 1));
     for (uint64_t i = 0; i < n; ++i) {
         uint64_t* hs = coords + i * A;
         const uint8_t* v = vals + val_off[i];
-        const uint8_t* end = v + val_len[i];
-        const uint8_t* ptr = v;
-        int ok = 1;
         uint64_t version = 0;
-        /* :174-181 version, :185-192 count */
-        if (ptr + 8 <= end) { version = be64(ptr); ptr += 8; } else ok = 0;
-        uint32_t count = 0;
-        if (ok && ptr + 2 <= end) { count = ((uint32_t)ptr[0] << 8) | ptr[1]; ptr += 2; } else ok = 0;
-        if (ok && count != A - 1) ok = 0; /* the schema's value attributes */
-        for (uint32_t k = 0; ok && k < count; ++k) {
-            /* :198-213; unlike the reference, the attribute must end inside the value */
-            if (ptr + 4 > end) { ok = 0; break; }
-            attr_n[k] = be32(ptr);
-            ptr += 4;
-            if ((uint64_t)(end - ptr) < attr_n[k]) { ok = 0; break; }
-            attr_p[k] = ptr;
-            ptr += attr_n[k];
-        }
+        const int ok = !hdxo_decode_value(v, val_len[i], A, &version, attr_o, attr_n);
         if (versions) versions[i] = ok ? version : 0;
         bad[i] = !ok;
         if (!ok) {
@@ -458,10 +469,11 @@ int64_t hdxo_hash_encoded(const uint32_t* types, uint32_t A, const uint8_t* keys
         int e;
         hs[0] = hdxo_hash_value(types[0], keys + key_off[i], key_len[i], &e);
         if (e) { nbad = -1; break; }
-        for (uint32_t k = 0; k + 1 < A && !e; ++k) hs[k + 1] = hdxo_hash_value(types[k + 1], attr_p[k], attr_n[k], &e);
+        for (uint32_t k = 0; k + 1 < A && !e; ++k)
+            hs[k + 1] = hdxo_hash_value(types[k + 1], v + attr_o[k], attr_n[k], &e);
         if (e) { nbad = -1; break; }
     }
-    free(attr_p);
+    free(attr_o);
     free(attr_n);
     return nbad;
 }

@@ -71,7 +71,11 @@ void hdxo_lookup_region(uint32_t D, uint32_t R, const uint16_t* attrs, const uin
  * coords[i*A+1+k] = hash(types[1+k], attribute k).  versions may be NULL.
  * bad[i] = 1 (and coords 0) when the value does not decode into A-1
  * attributes inside its bytes; returns the number of such objects, or -1 on
- * an unknown type / mis-sized numeric. */
+ * an unknown type / mis-sized numeric.  hdxo_decode_value is the decoding
+ * alone for one value under a schema of A attributes: 0 with *version and the
+ * A-1 slices as off[k] (from the value's start) / n[k], or 1. */
+int hdxo_decode_value(const uint8_t* v, uint32_t len, uint32_t A, uint64_t* version, uint64_t* off,
+                      uint32_t* n);
 int64_t hdxo_hash_encoded(const uint32_t* types, uint32_t A, const uint8_t* keys,
                           const uint64_t* key_off, const uint32_t* key_len, const uint8_t* vals,
                           const uint64_t* val_off, const uint32_t* val_len, uint64_t n,

@@ -13,6 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
 _REF = None
 _REF_HASH = None
+_REF_STORE = None
 
 
 def build():
@@ -54,6 +55,8 @@ def lib():
         L.hdxo_search_regions.restype = ctypes.c_int
         L.hdxo_search_regions.argtypes = [u32, u32, vp, vp, vp, vp, vp, u32, vp]
         L.hdxo_hash_encoded.restype = ctypes.c_int64
+        L.hdxo_decode_value.restype = ctypes.c_int
+        L.hdxo_decode_value.argtypes = [vp, u32, u32, ctypes.POINTER(u64), vp, vp]
         _LIB = L
     return _LIB
 
@@ -92,6 +95,106 @@ def ref_hash_lib():
         R.ref_hash_object.restype = ctypes.c_int
         _REF_HASH = R
     return _REF_HASH
+
+
+def ref_store_lib():
+    """oracle/_ref/libref_store.so (the reference's daemon/datalayer_encodings.cc,
+    daemon/index_{int64,float,timestamp}.cc and admin/partition.cc behind
+    ref_store_glue.cc), or None."""
+    global _REF_STORE
+    if _REF_STORE is None:
+        path = os.path.join(_HERE, "_ref", "libref_store.so")
+        if not os.path.exists(path):
+            return None
+        R = ctypes.CDLL(path)
+        u64, u32, i32, vp = ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int32, ctypes.c_void_p
+        R.ref_decode_value.argtypes = [vp, u64, u64, ctypes.POINTER(i32), ctypes.POINTER(u64), ctypes.POINTER(u64),
+                                       vp, vp]
+        R.ref_decode_value.restype = ctypes.c_int
+        R.ref_rc_success.restype = i32
+        R.ref_rc_bad_encoding.restype = i32
+        R.ref_encode_value.argtypes = [vp, vp, vp, u32, u64, vp, u64]
+        R.ref_encode_value.restype = u64
+        R.ref_index_encoded_size.argtypes = [u32, vp, u64]
+        R.ref_index_encoded_size.restype = ctypes.c_int64
+        R.ref_index_encode.argtypes = [u32, vp, u64, vp, ctypes.POINTER(u64)]
+        R.ref_index_encode.restype = ctypes.c_int
+        R.ref_partition.argtypes = [u32, u32, ctypes.POINTER(u64), vp, vp, u64]
+        R.ref_partition.restype = ctypes.c_int
+        _REF_STORE = R
+    return _REF_STORE
+
+
+def ref_decode_value(vals, off=0, length=None, max_attrs=None):
+    """The reference's decode_value on vals[off:off + length] (a uint8 array,
+    read in place) -> (success, version, count, [(offset, length)]): success is
+    SUCCESS as against BAD_ENCODING, count is attrs.size() either way and each
+    slice is reported from the value's start.  No slice is dereferenced."""
+    R = ref_store_lib()
+    vals = np.ascontiguousarray(vals, np.uint8)
+    length = len(vals) - off if length is None else int(length)
+    assert 0 <= off and off + length <= len(vals)
+    if max_attrs is None:
+        max_attrs = max((length - 10) // 4, 0) + 1  # every decoded slice has a 4-byte prefix inside the value
+    offs = np.zeros(max(max_attrs, 1), np.uint64)
+    lens = np.zeros(max(max_attrs, 1), np.uint64)
+    rc, version, count = ctypes.c_int32(-1), ctypes.c_uint64(0), ctypes.c_uint64(0)
+    buf = vals if vals.size else np.zeros(1, np.uint8)
+    err = R.ref_decode_value(buf.ctypes.data + off, length, max_attrs, ctypes.byref(rc), ctypes.byref(version),
+                             ctypes.byref(count), offs.ctypes.data, lens.ctypes.data)
+    assert err == 0 and rc.value in (R.ref_rc_success(), R.ref_rc_bad_encoding())
+    k = min(count.value, max_attrs)
+    return (rc.value == R.ref_rc_success(), version.value, count.value,
+            list(zip(offs[:k].tolist(), lens[:k].tolist())))
+
+
+def ref_encode_value(attrs, version):
+    """The reference's encode_value over the attribute values `attrs` (a list of bytes) -> bytes."""
+    R = ref_store_lib()
+    blob = np.frombuffer(b"".join(attrs) + b"\0", np.uint8)
+    lens = np.array([len(a) for a in attrs], np.uint32)
+    off = np.zeros(max(len(attrs), 1), np.uint64)
+    off[1:len(attrs)] = np.cumsum(lens[:-1], dtype=np.uint64)
+    lens = lens if lens.size else np.zeros(1, np.uint32)
+    size = 10 + sum(4 + len(a) for a in attrs)
+    out = np.zeros(size + 16, np.uint8)
+    got = R.ref_encode_value(blob.ctypes.data, off.ctypes.data, lens.ctypes.data, len(attrs), version,
+                             out.ctypes.data, len(out))
+    assert got <= len(out), "the reference's encode_value wrote %d bytes, %d expected" % (got, size)
+    return out[:got].tobytes()
+
+
+def ref_index_encode(type_id: int, data: bytes):
+    """The reference's index_encoding::lookup(type)->encode(value) -> (key
+    bytes, err): err 1: no numeric encoder for the type, 2: a value neither
+    empty nor 8 bytes (datatype_*::hash asserts, so the glue refuses it)."""
+    buf = ctypes.create_string_buffer(bytes(data), max(len(data), 1))
+    out = ctypes.create_string_buffer(16)
+    written = ctypes.c_uint64(0)
+    err = ref_store_lib().ref_index_encode(type_id, buf, len(data), out, ctypes.byref(written))
+    return out.raw[:written.value], err
+
+
+def ref_index_encoded_size(type_id: int, data: bytes) -> int:
+    """The reference's encoded_size(value); -1 for a type without a numeric encoder."""
+    buf = ctypes.create_string_buffer(bytes(data), max(len(data), 1))
+    return ref_store_lib().ref_index_encoded_size(type_id, buf, len(data))
+
+
+def ref_partition(num_attrs, num_servers):
+    """The reference's partition() -> (lower, upper) as (R, num_attrs) uint64
+    arrays, or None where it asserts (no attributes) or divides by zero (no
+    servers)."""
+    R = ref_store_lib()
+    count = ctypes.c_uint64(0)
+    if R.ref_partition(num_attrs, num_servers, ctypes.byref(count), None, None, 0) != 0:
+        return None
+    n = count.value
+    lower = np.zeros(max(n * num_attrs, 1), np.uint64)
+    upper = np.zeros(max(n * num_attrs, 1), np.uint64)
+    err = R.ref_partition(num_attrs, num_servers, ctypes.byref(count), lower.ctypes.data, upper.ctypes.data, n)
+    assert err == 0 and count.value == n
+    return lower[:n * num_attrs].reshape(n, num_attrs), upper[:n * num_attrs].reshape(n, num_attrs)
 
 
 def ref_hash(type_id: int, data: bytes):
@@ -231,6 +334,23 @@ def hash_encoded(types, keys, key_off, key_len, vals, val_off, val_len):
                                 bad.ctypes.data)
     assert r >= 0
     return coords.reshape(n, A), versions[:n], bad[:n].astype(bool)
+
+
+def decode_value(A: int, vals, off=0, length=None):
+    """The oracle's decode of vals[off:off + length] (a uint8 array) under a
+    schema of A attributes -> (ok, version, [(offset, length)] from the
+    value's start); (False, 0, []) where it refuses the value."""
+    vals = np.ascontiguousarray(vals, np.uint8)
+    length = len(vals) - off if length is None else int(length)
+    assert 0 <= off and off + length <= len(vals)
+    offs = np.zeros(max(A, 1), np.uint64)
+    lens = np.zeros(max(A, 1), np.uint32)
+    version = ctypes.c_uint64(0)
+    buf = vals if vals.size else np.zeros(1, np.uint8)
+    if lib().hdxo_decode_value(buf.ctypes.data + off, length, A, ctypes.byref(version), offs.ctypes.data,
+                               lens.ctypes.data):
+        return False, 0, []
+    return True, version.value, list(zip(offs[:A - 1].tolist(), lens[:A - 1].tolist()))
 
 
 def index_encode(type_id: int, data: bytes):
