@@ -91,6 +91,12 @@ SIGNATURES = [
     ("hdx_hash_batch_regions_device", _i32, [_vp, _u32, _vp, _vp, _vp, _u64, _vp, _u32, _vp, _vp, _vp, _vp]),
     ("hdx_index_key_size", ctypes.c_size_t, [_u32]),
     ("hdx_index_encode_device", _i32, [_u32, _vp, _vp, _vp, _u64, _vp, _vp, _vp]),
+    ("hdx_index_entry", _i32, [_vp, _u32, _vp, _sz, _u32, _vp, _sz, _vp, _sz, _vp]),
+    ("hdx_index_entries_plan_device", _i32, [_vp, _u32, _vp, _vp, _vp, _vp, _u64, _vp, _u32, _vp, _vp, _vp, _vp,
+                                             _vp]),
+    ("hdx_index_entries_fill_device", _i32, [_vp, _u32, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _u32, _vp, _vp, _vp,
+                                             _vp, _u64, _vp, _vp]),
+    ("hdx_index_scan_block", _u32, []),
     ("hdx_search_regions", _i32, [_vp, _vp, _u32, _vp, _vp, _vp]),
     ("hdx_search_space", _i32, [_vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp, _vp]),
     ("hdx_batcher_create", _i32, [_vp, _u32, _vp, _vp]),

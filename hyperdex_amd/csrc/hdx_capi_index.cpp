@@ -90,6 +90,106 @@ HDX_EXPORT hdx_status hdx_index_encode_device(uint32_t type, const uint8_t* blob
     return HDX_OK;
 }
 
+// ---- index entries of stored objects (hdx_index_entries.hip) ---------------
+
+namespace {
+
+// Everything both entry points check before the device is touched, and the
+// kernel arguments the specs give.
+hdx_status entries_args(IndexEntriesArgs& a, const uint32_t* types, uint32_t attrs_sz, const hdx_index_spec* specs,
+                        uint32_t m) {
+    hdx_status st = check_schema(types, attrs_sz, nullptr);
+    if (st != HDX_OK) return st;
+    if (!specs) return fail(HDX_E_INVALID, "specs is NULL");
+    if (m == 0 || m > HDX_MAX_INDICES) return fail(HDX_E_INVALID, "m=%u outside [1, %d]", m, HDX_MAX_INDICES);
+    a = IndexEntriesArgs{};
+    for (uint32_t k = 0; k < m; ++k) {
+        const hdx_index_spec& s = specs[k];
+        if (s.attr == 0 || s.attr >= attrs_sz)
+            return fail(HDX_E_INVALID, "index %u: attribute %u outside [1, %u)", k, s.attr, attrs_sz);
+        if (s.prefix_len == 0 || s.prefix_len > HDX_INDEX_PREFIX_MAX)
+            return fail(HDX_E_INVALID, "index %u: prefix_len %u outside [1, %d]", k, s.prefix_len,
+                        HDX_INDEX_PREFIX_MAX);
+    }
+    if (!(a.key_enc = entry_encoder(types[0])))
+        return fail(HDX_E_BADTYPE, "key: hyperdatatype %u has no primitive index encoding", types[0]);
+    for (uint32_t k = 0; k < m; ++k) {
+        const hdx_index_spec& s = specs[k];
+        if (!(a.enc[k] = entry_encoder(types[s.attr])))
+            return fail(HDX_E_BADTYPE, "index %u: hyperdatatype %u of attribute %u has no primitive index encoding",
+                        k, types[s.attr], s.attr);
+        a.attr[k] = s.attr;
+        a.plen[k] = s.prefix_len;
+        std::memcpy(a.prefix + k * kIndexPrefixStride, s.prefix, s.prefix_len);
+    }
+    a.A = attrs_sz;
+    a.m = m;
+    return HDX_OK;
+}
+
+}  // namespace
+
+HDX_EXPORT uint32_t hdx_index_scan_block(void) { return kIndexScanBlock; }
+
+HDX_EXPORT hdx_status hdx_index_entries_plan_device(const uint32_t* types, uint32_t attrs_sz,
+                                                    const uint32_t* key_len, const uint8_t* vals,
+                                                    const uint64_t* val_off, const uint32_t* val_len, uint64_t n,
+                                                    const hdx_index_spec* specs, uint32_t m, uint32_t* attr_off,
+                                                    uint32_t* attr_len, uint64_t* entry_off, uint32_t* status_dev,
+                                                    hdx_stream stream) {
+    IndexEntriesArgs a;
+    hdx_status st = entries_args(a, types, attrs_sz, specs, m);
+    if (st != HDX_OK) return st;
+    if (!key_len || !vals || !val_off || !val_len || !attr_off || !attr_len || !entry_off)
+        return fail(HDX_E_INVALID, "NULL device pointer");
+    if (n > (UINT64_MAX >> 8) / m) return fail(HDX_E_INVALID, "n * m overflows");
+    if ((st = bind_device(-1)) != HDX_OK) return st;
+    a.key_len = key_len;
+    a.vals = vals;
+    a.val_off = val_off;
+    a.val_len = val_len;
+    a.attr_off = attr_off;
+    a.attr_len = attr_len;
+    a.entry_off = entry_off;
+    a.status = status_dev;
+    a.n = n;
+    bool no_scratch = false;
+    HIP_TRY(launch_index_entries_plan(a, (hipStream_t)stream, &no_scratch));
+    if (no_scratch) return fail(HDX_E_NOMEM, "scan scratch for %llu entries", (unsigned long long)(n * m));
+    return HDX_OK;
+}
+
+HDX_EXPORT hdx_status hdx_index_entries_fill_device(const uint32_t* types, uint32_t attrs_sz, const uint8_t* keys,
+                                                    const uint64_t* key_off, const uint32_t* key_len,
+                                                    const uint8_t* vals, const uint64_t* val_off, uint64_t n,
+                                                    const hdx_index_spec* specs, uint32_t m,
+                                                    const uint32_t* attr_off, const uint32_t* attr_len,
+                                                    const uint64_t* entry_off, uint8_t* entries,
+                                                    uint64_t entries_bytes, uint32_t* status_dev,
+                                                    hdx_stream stream) {
+    IndexEntriesArgs a;
+    hdx_status st = entries_args(a, types, attrs_sz, specs, m);
+    if (st != HDX_OK) return st;
+    if (!keys || !key_off || !key_len || !vals || !val_off || !attr_off || !attr_len || !entry_off || !entries)
+        return fail(HDX_E_INVALID, "NULL device pointer");
+    if (n > (UINT64_MAX >> 8) / m) return fail(HDX_E_INVALID, "n * m overflows");
+    if ((st = bind_device(-1)) != HDX_OK) return st;
+    a.keys = keys;
+    a.key_off = key_off;
+    a.key_len = key_len;
+    a.vals = vals;
+    a.val_off = val_off;
+    a.attr_off = const_cast<uint32_t*>(attr_off);
+    a.attr_len = const_cast<uint32_t*>(attr_len);
+    a.entry_off = const_cast<uint64_t*>(entry_off);
+    a.entries = entries;
+    a.entries_bytes = entries_bytes;
+    a.status = status_dev;
+    a.n = n;
+    HIP_TRY(launch_index_entries_fill(a, (hipStream_t)stream));
+    return HDX_OK;
+}
+
 HDX_EXPORT hdx_status hdx_search_regions(hdx_region_table t, const hdx_range* ranges, uint32_t nranges,
                                          const uint8_t* has_replicas, uint8_t* include, int* cleared) {
     if (!t || !cleared || (nranges && !ranges) || (t->R && !include))

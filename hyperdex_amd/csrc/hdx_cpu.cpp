@@ -246,3 +246,58 @@ HDX_EXPORT hdx_status hdx_hash_object(const uint32_t* types, uint32_t attrs_sz, 
         (void)cpu::hash_code(type_code(types[j]), values[j - 1], value_lens[j - 1], &hs[j]);
     return HDX_OK;
 }
+
+// ---- one object's secondary-index entry (include/hdxhash.h) ----------------
+
+namespace {
+
+// enc(type, value) written at out (ENC_*, hdx_host_common.h)
+uint8_t* entry_encode(uint32_t enc, const uint8_t* p, size_t len, uint8_t* out) {
+    if (enc == ENC_STRING) {
+        if (len) memcpy(out, p, len);
+        return out + len;
+    }
+    const uint64_t bits = len ? cpu::le64(p) : 0;
+    const uint64_t be = __builtin_bswap64(enc == ENC_INT64 ? cpu::ordered_int64(bits) : cpu::ordered_double(bits));
+    memcpy(out, &be, 8);
+    if (enc == ENC_INT64) return out + 8;
+    memcpy(out + 8, &bits, 8);  // packdoublele(number): 0.0 when empty
+    return out + 16;
+}
+
+}  // namespace
+
+// index_primitive::index_entry(ri, ii, key_ie, key, value, ..), daemon/index_primitive.cc:291-329,
+// with the caller's prefix standing for 'i' ++ varint(ri) ++ varint(ii)
+HDX_EXPORT hdx_status hdx_index_entry(const hdx_index_spec* spec, uint32_t key_type, const uint8_t* key,
+                                      size_t key_len, uint32_t attr_type, const uint8_t* value, size_t value_len,
+                                      uint8_t* out, size_t out_cap, size_t* out_len) {
+    if (out_len) *out_len = 0;
+    if (!spec || !out_len || (!key && key_len) || (!value && value_len) || (!out && out_cap))
+        return fail(HDX_E_INVALID, "NULL pointer");
+    if (spec->attr == 0) return fail(HDX_E_INVALID, "an index names attribute 0 (the key)");
+    if (spec->prefix_len == 0 || spec->prefix_len > HDX_INDEX_PREFIX_MAX)
+        return fail(HDX_E_INVALID, "prefix_len %u outside [1, %d]", spec->prefix_len, HDX_INDEX_PREFIX_MAX);
+    const uint32_t kenc = entry_encoder(key_type), venc = entry_encoder(attr_type);
+    if (!kenc) return fail(HDX_E_BADTYPE, "key: hyperdatatype %u has no primitive index encoding", key_type);
+    if (!venc) return fail(HDX_E_BADTYPE, "hyperdatatype %u has no primitive index encoding", attr_type);
+    // encoded_size() of a numeric does not look at the value (index_int64.cc, index_float.cc): the
+    // entry's size is known, and reported, even where encode() would assert
+    const size_t key_sz = entry_encoded_size(kenc, key_len), val_sz = entry_encoded_size(venc, value_len);
+    const bool variable = kenc == ENC_STRING && venc == ENC_STRING;  // !encoding_fixed() for both (:302)
+    const size_t sz = spec->prefix_len + val_sz + key_sz + (variable ? 4 : 0);
+    *out_len = sz;
+    if (kenc != ENC_STRING && key_len != 0 && key_len != 8)
+        return fail(HDX_E_BADSIZE, "key: numeric value of %zu bytes", key_len);
+    if (venc != ENC_STRING && value_len != 0 && value_len != 8)
+        return fail(HDX_E_BADSIZE, "numeric value of %zu bytes", value_len);
+    if (out_cap < sz) return fail(HDX_E_NOMEM, "entry of %zu bytes, room for %zu", sz, out_cap);
+    memcpy(out, spec->prefix, spec->prefix_len);
+    uint8_t* p = entry_encode(venc, value, value_len, out + spec->prefix_len);
+    p = entry_encode(kenc, key, key_len, p);
+    if (variable) {
+        const uint32_t be = __builtin_bswap32((uint32_t)key_sz);  // pack32be(key_sz), :322-325
+        memcpy(p, &be, 4);
+    }
+    return HDX_OK;
+}

@@ -44,6 +44,28 @@ inline int type_code(uint32_t t) {
             return -1;
     }
 }
+// The index encoder of a key or an indexed attribute in a secondary-index
+// entry (daemon/index_info.cc:77-118), shared by the per-object CPU form
+// (hdx_cpu.cpp) and the device entry points (hdx_capi_index.cpp,
+// hdx_index_entries.hip): the bytes themselves (index_string.cc:62-79), the
+// 8-byte ordered int64 (index_int64.cc:76-79; the timestamps delegate to it,
+// index_timestamp.cc:79-82), the 16-byte float key (index_float.cc:69-90).
+enum : uint8_t { ENC_NONE = 0, ENC_STRING = 1, ENC_INT64 = 2, ENC_FLOAT = 3 };
+// ENC_NONE: unknown types and the container, document and macaroon types,
+// whose indices write one entry per element or none.
+inline uint8_t entry_encoder(uint32_t type) {
+    const int c = type_code(type);
+    if (c == (int)CODE_STRING) return ENC_STRING;
+    if (c == (int)CODE_INT64) return ENC_INT64;
+    if (c == (int)CODE_FLOAT) return ENC_FLOAT;
+    if (c >= (int)CODE_TS_SECOND && c <= (int)CODE_TS_MONTH) return ENC_INT64;
+    return ENC_NONE;
+}
+// Bytes of enc(type, value) for a value of len bytes.
+inline uint64_t entry_encoded_size(uint32_t enc, uint64_t len) {
+    return enc == ENC_STRING ? len : enc == ENC_INT64 ? 8 : 16;
+}
+
 // Sets the calling thread's hdx_last_error() text and returns s.
 hdx_status fail(hdx_status s, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 

@@ -134,7 +134,7 @@ hipError_t launch_lookup_region(const RegionArgs& a, hipStream_t stream);
 using RegionHashFn = std::function<hipError_t(uint64_t first, uint64_t count, uint64_t* coords)>;
 constexpr uint64_t kRegionChunkBytes = 2ull << 30;
 constexpr uint64_t kRegionLookupMinObjects = 1ull << 20;
-void trim_region_pools();  // hdx_regions.hip: release the regions scratch pools' cached memory
+void trim_scratch_pools();  // hdx_regions.hip: release the scratch pools' cached memory (scratch_pool, below)
 bool regions_by_lookup_pays(uint64_t n);
 uint64_t regions_chunk_objects(uint64_t n, uint32_t A);
 hipError_t regions_by_lookup(uint64_t n, uint32_t A, const SweepTable* t, uint32_t T, uint64_t* coords,
@@ -222,6 +222,44 @@ struct IndexArgs {
 };
 
 hipError_t launch_index_encode(const IndexArgs& a, hipStream_t stream);
+
+// Secondary-index entries of stored objects (hdx_index_entries.hip): m
+// indices over n stored objects, entry e = i*m + k.  enc[] / key_enc hold the
+// index encoder of each indexed attribute and of the key (ENC_*,
+// hdx_host_common.h).
+constexpr uint32_t kIndexScanBlock = 1024;  // elements per workgroup of the entry-size prefix sum
+constexpr uint32_t kIndexPrefixStride = 24; // >= HDX_INDEX_PREFIX_MAX
+struct IndexEntriesArgs {
+    const uint8_t* keys;      // fill only
+    const uint64_t* key_off;  // fill only
+    const uint32_t* key_len;
+    const uint8_t* vals;
+    const uint64_t* val_off;
+    const uint32_t* val_len;  // plan only
+    uint32_t* attr_off;       // [n*m] plan writes, fill reads
+    uint32_t* attr_len;       // [n*m]
+    uint64_t* entry_off;      // [n*m + 1]
+    uint8_t* entries;         // fill only
+    uint64_t entries_bytes;
+    uint32_t* status;         // may be NULL
+    uint64_t n;
+    uint32_t A, m;
+    uint32_t key_enc;
+    uint16_t attr[HDX_MAX_INDICES];
+    uint8_t enc[HDX_MAX_INDICES];
+    uint8_t plen[HDX_MAX_INDICES];
+    uint8_t prefix[HDX_MAX_INDICES * kIndexPrefixStride];
+};
+// The walk (a lane per object), then the exclusive prefix sum of the entry
+// sizes over n*m + 1 elements, reduce-then-scan in separate launches.  Its
+// block sums come from the library's stream-ordered pool (scratch_pool); if
+// that allocation fails nothing is launched and *no_scratch is set.
+hipError_t launch_index_entries_plan(const IndexEntriesArgs& a, hipStream_t stream, bool* no_scratch);
+hipError_t launch_index_entries_fill(const IndexEntriesArgs& a, hipStream_t stream);
+// hdx_regions.hip: the library's per-device memory pool for stream-ordered
+// scratch (the regions' coordinate chunks and this scan's block sums), on the
+// calling thread's current device.
+hipError_t scratch_pool(hipMemPool_t* out);
 
 // Search pruning (hdx_index.hip) over one subspace's region table: m ranges
 // that name a subspace attribute, in the order lookup_search visits them.

@@ -122,14 +122,16 @@ uint64_t regions_chunk_objects(uint64_t n, uint32_t A) {
     return std::min<uint64_t>(n, std::max<uint64_t>(1, bytes / (8ull * A)));
 }
 
-// The regions scratch comes from a memory pool of the library's own per
-// device that keeps up to one chunk cached between calls (the device's default
-// pool returns freed memory at every synchronisation, so each call would map
-// its chunk afresh); the pool is trimmed at hdx_shutdown.
+// Stream-ordered scratch of the library — the regions' coordinate chunks
+// (below) and the block sums of the index entries' prefix sum
+// (hdx_index_entries.hip) — comes from a memory pool of the library's own per
+// device that keeps up to one region chunk cached between calls (the device's
+// default pool returns freed memory at every synchronisation, so each call
+// would map its scratch afresh); the pools are trimmed at hdx_shutdown.
 static std::mutex g_pool_mu;
 static hipMemPool_t g_pool[64];
 
-static hipError_t region_pool(hipStream_t stream, hipMemPool_t* out) {
+hipError_t scratch_pool(hipMemPool_t* out) {
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
@@ -147,12 +149,11 @@ static hipError_t region_pool(hipStream_t stream, hipMemPool_t* out) {
         uint64_t keep = kRegionChunkBytes;
         (void)hipMemPoolSetAttribute(g_pool[dev], hipMemPoolAttrReleaseThreshold, &keep);
     }
-    (void)stream;
     *out = g_pool[dev];
     return hipSuccess;
 }
 
-void trim_region_pools() {
+void trim_scratch_pools() {
     std::lock_guard<std::mutex> lk(g_pool_mu);
     for (hipMemPool_t p : g_pool)
         if (p) (void)hipMemPoolTrimTo(p, 0);
@@ -167,7 +168,7 @@ hipError_t regions_by_lookup(uint64_t n, uint32_t A, const SweepTable* t, uint32
     hipError_t e = hipSuccess;
     if (!coords) {
         hipMemPool_t pool = nullptr;
-        e = region_pool(stream, &pool);
+        e = scratch_pool(&pool);
         if (e == hipSuccess) e = hipMallocFromPoolAsync((void**)&scratch, chunk * A * 8, pool, stream);
 #if HDX_DEBUG_BUILD
         if (e == hipSuccess && hash_variant() == 247) {  // tests: the allocation "fails"

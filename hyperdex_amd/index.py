@@ -114,3 +114,149 @@ def search_space(tables: Sequence[RegionTable], ranges: Sequence[tuple],
     mask = include[:len(tables[c].ids)] if c >= 0 else include[:0]
     assert c < 0 or int(mask.sum()) == servers.value
     return c, mask, bool(cleared.value)
+
+
+# ---- secondary-index entries of stored objects (hdx_index_entries_*) ---------
+
+HDX_MAX_INDICES = 32
+HDX_INDEX_PREFIX_MAX = 21
+
+
+class _Spec(ctypes.Structure):
+    """hdx_index_spec (include/hdxhash.h)."""
+    _fields_ = [("attr", ctypes.c_uint16), ("prefix_len", ctypes.c_uint8),
+                ("prefix", ctypes.c_uint8 * HDX_INDEX_PREFIX_MAX)]
+
+
+class IndexSpec:
+    """One index: the schema attribute it is on (1 .. A-1) and its entries'
+    prefix 'i' ++ varint(region) ++ varint(index id), which the daemon's own
+    index_entry(ri, ii, &scratch, &slice) (daemon/index_primitive.cc:209-230)
+    produces; this package never encodes a varint."""
+
+    def __init__(self, attr: int, prefix: bytes):
+        self.attr, self.prefix = int(attr), bytes(prefix)
+
+    def c(self) -> _Spec:
+        """The C struct; values the struct cannot hold are passed through as
+        out-of-range ones, so the library refuses them."""
+        s = _Spec()
+        s.attr = self.attr if 0 <= self.attr < 65536 else 0
+        n = len(self.prefix)
+        s.prefix_len = n if n <= HDX_INDEX_PREFIX_MAX else 255
+        ctypes.memmove(s.prefix, self.prefix, min(n, HDX_INDEX_PREFIX_MAX))
+        return s
+
+
+def _specs(specs):
+    arr = (_Spec * max(len(specs), 1))()
+    for k, s in enumerate(specs):
+        arr[k] = s.c()
+    return arr
+
+
+def scan_block() -> int:
+    return int(lib().hdx_index_scan_block())
+
+
+def __getattr__(name):  # SCAN_BLOCK: read from the library on first use (it may not be built at import)
+    if name == "SCAN_BLOCK":
+        return scan_block()
+    raise AttributeError(name)
+
+
+def index_entry(spec: IndexSpec, key_type: int, key: bytes, attr_type: int, value: bytes) -> bytes:
+    """One object's entry under one index on the host CPU (hdx_index_entry):
+    prefix ++ enc(attr_type, value) ++ enc(key_type, key) [++ u32 BE key size
+    when both are STRING], index_primitive::index_entry's bytes."""
+    c = spec.c()
+    need = ctypes.c_size_t(0)
+    cap = len(spec.prefix) + len(value) + len(key) + 40
+    out = ctypes.create_string_buffer(cap)
+    check(lib().hdx_index_entry(ctypes.byref(c), key_type, key, len(key), attr_type, value, len(value), out, cap,
+                                ctypes.byref(need)))
+    return out.raw[:need.value]
+
+
+def _torch_stream(stream, device):
+    import torch
+    if stream is None:
+        return torch.cuda.current_stream(device)
+    if hasattr(stream, "cuda_stream"):
+        return stream
+    return torch.cuda.ExternalStream(stream, device=device)
+
+
+def _types(types):
+    return np.ascontiguousarray(np.asarray(types, dtype=np.uint32))
+
+
+def index_entries_plan(types, key_len, vals, val_off, val_len, specs, status=None, stream=None):
+    """hdx_index_entries_plan_device on torch HIP tensors: returns (attr_off
+    i32[n*m], attr_len i32[n*m], entry_off i64[n*m + 1]) — u32 / u64 bit
+    patterns; entry_off[-1] is the total size of the entries."""
+    import torch
+
+    t = _types(types)
+    n, m = val_off.numel(), len(specs)
+    dev = val_off.device
+    for x in (key_len, vals, val_off, val_len):
+        assert x.is_cuda and x.is_contiguous()
+    assert val_len.numel() == n and key_len.numel() == n
+    s = _torch_stream(stream, dev)
+    with torch.cuda.stream(s):
+        attr_off = torch.empty(max(n * m, 1), dtype=torch.int32, device=dev)
+        attr_len = torch.empty(max(n * m, 1), dtype=torch.int32, device=dev)
+        entry_off = torch.empty(n * m + 1, dtype=torch.int64, device=dev)
+    # an empty batch is planned (and its types and specs checked) like any other: tensors without
+    # elements have no address, so entry_off stands in for them; nothing reads it when n == 0
+    key_len, vals, val_off, val_len = [x if x.numel() else entry_off for x in (key_len, vals, val_off, val_len)]
+    check(lib().hdx_index_entries_plan_device(
+        t.ctypes.data, len(t), key_len.data_ptr(), vals.data_ptr(), val_off.data_ptr(), val_len.data_ptr(), n,
+        _specs(specs), m, attr_off.data_ptr(), attr_len.data_ptr(), entry_off.data_ptr(),
+        status.data_ptr() if status is not None else None, s.cuda_stream))
+    return attr_off[:n * m], attr_len[:n * m], entry_off
+
+
+def index_entries_fill(types, keys, key_off, key_len, vals, val_off, specs, attr_off, attr_len, entry_off,
+                       entries, status=None, stream=None):
+    """hdx_index_entries_fill_device: writes entry e at entries[entry_off[e]:]
+    (`entries` a contiguous uint8 HIP tensor, any alignment); with fewer than
+    entry_off[-1] bytes nothing is written and status gets HDX_E_NOMEM's bit."""
+    t = _types(types)
+    n, m = val_off.numel(), len(specs)
+    for x in (keys, key_off, key_len, vals, val_off, attr_off, attr_len, entry_off, entries):
+        assert x.is_cuda and x.is_contiguous()
+    assert entries.element_size() == 1 and entry_off.numel() == n * m + 1
+    s = _torch_stream(stream, val_off.device)
+    check(lib().hdx_index_entries_fill_device(
+        t.ctypes.data, len(t), keys.data_ptr(), key_off.data_ptr(), key_len.data_ptr(), vals.data_ptr(),
+        val_off.data_ptr(), n, _specs(specs), m, attr_off.data_ptr(), attr_len.data_ptr(), entry_off.data_ptr(),
+        entries.data_ptr(), entries.numel(), status.data_ptr() if status is not None else None, s.cuda_stream))
+    return entries
+
+
+def index_entries(types, keys, key_off, key_len, vals, val_off, val_len, specs, status=None, stream=None):
+    """Every stored object's entry under every index of `specs`, on the device:
+    plan, one read of the total, the allocation, fill — launches and the read
+    on `stream` only.  Returns (entries u8[total], entry_off i64[n*m + 1]):
+    entry e = i*m + k is entries[entry_off[e] : entry_off[e+1]].  An object
+    that does not decode, or whose key or an indexed attribute is a numeric
+    of neither 0 nor 8 bytes, has empty entries (status: HDX_E_BADENC /
+    HDX_E_BADSIZE bits)."""
+    import torch
+
+    dev = val_off.device
+    s = _torch_stream(stream, dev)
+    attr_off, attr_len, entry_off = index_entries_plan(types, key_len, vals, val_off, val_len, specs, status, s)
+    if val_off.numel() == 0:  # planned, so types and specs are checked; there is nothing to fill
+        return torch.empty(0, dtype=torch.uint8, device=dev), entry_off
+    with torch.cuda.stream(s):
+        host = torch.empty(1, dtype=torch.int64, pin_memory=True)
+        host.copy_(entry_off[-1:], non_blocking=True)
+        s.synchronize()
+        total = int(host.item())
+        entries = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+    index_entries_fill(types, keys, key_off, key_len, vals, val_off, specs, attr_off, attr_len, entry_off,
+                       entries, status, s)
+    return entries[:total], entry_off

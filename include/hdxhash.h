@@ -373,6 +373,105 @@ hdx_status hdx_index_encode_device(uint32_t type, const uint8_t* blob, const uin
                                    const uint32_t* len, uint64_t n, uint8_t* out,
                                    uint32_t* status_dev, hdx_stream stream);
 
+/* ---- secondary-index entries of stored objects (SURVEY note 3) ----------- */
+
+/* What datalayer::indexer_thread Puts per stored object and index
+ * (daemon/datalayer_indexer_thread.cc:361-399 -> create_index_changes,
+ * daemon/datalayer_encodings.cc:283-318, with old_value == NULL ->
+ * index_primitive::index_changes -> index_entry, daemon/index_primitive.cc:
+ * 53-80, 291-329).  For object i with external key `key` and an index k on
+ * attribute a_k (1 <= a_k < attrs_sz) whose slice of the value is `value`:
+ *
+ *   entry(i,k) = prefix_k                      'i' ++ varint(region) ++ varint(index id)
+ *             ++ enc(types[a_k], value)        m_ie->encode
+ *             ++ enc(types[0], key)            key_ie->encode
+ *             ++ u32 BE size of enc(types[0], key)   ONLY when types[a_k] and types[0]
+ *                                              are both STRING (neither encoding is
+ *                                              fixed, index_primitive.cc:302, 322-325)
+ *   enc(STRING, v)               = v's bytes             (daemon/index_string.cc:62-79)
+ *   enc(INT64 | TIMESTAMP_*, v)  = the 8-byte key of hdx_index_encode_device
+ *   enc(FLOAT, v)                = its 16-byte key
+ *
+ * The prefix is the caller's, as bytes: it is constant per (region, index),
+ * the daemon's own index_entry(ri, ii, &scratch, &slice) (index_primitive.cc:
+ * 209-230) produces it, and this library never encodes a varint.
+ *
+ * Out of scope: container and document indices (index_list / set / map /
+ * document write one entry per element) — an indexed attribute or a key of
+ * any type other than STRING, INT64, FLOAT or TIMESTAMP_* is HDX_E_BADTYPE
+ * before any launch; the delete half of index_changes (old_value); a
+ * host-resident (_host) pipeline; the device set. */
+#define HDX_MAX_INDICES 32
+#define HDX_INDEX_PREFIX_MAX 21            /* 'i' + two varint64 of at most 10 bytes */
+typedef struct hdx_index_spec {
+    uint16_t attr;                          /* 1 .. attrs_sz-1 (create_index_changes asserts attr > 0) */
+    uint8_t  prefix_len;                    /* 1 .. HDX_INDEX_PREFIX_MAX */
+    uint8_t  prefix[HDX_INDEX_PREFIX_MAX];
+} hdx_index_spec;
+
+/* One object's entry under one index, on the host CPU (the daemon's per-op
+ * put builds its entries on its own core): no allocation, no device.  Always
+ * sets *out_len to the entry's size — also with HDX_E_NOMEM and HDX_E_BADSIZE
+ * (a numeric's encoded size does not depend on its value); only where no size
+ * exists, HDX_E_BADTYPE and HDX_E_INVALID, it is 0 — and writes the entry when
+ * out_cap holds it.  HDX_E_NOMEM when out_cap is too small, HDX_E_BADSIZE for
+ * a numeric key or value of neither 0 nor 8 bytes (the reference asserts),
+ * HDX_E_BADTYPE for a key or attribute type other than STRING / INT64 / FLOAT
+ * / TIMESTAMP_*, HDX_E_INVALID for a NULL pointer, spec->attr == 0 or a
+ * prefix_len outside 1..HDX_INDEX_PREFIX_MAX; nothing is written with any of
+ * them. */
+hdx_status hdx_index_entry(const hdx_index_spec* spec, uint32_t key_type, const uint8_t* key, size_t key_len,
+                           uint32_t attr_type, const uint8_t* value, size_t value_len, uint8_t* out,
+                           size_t out_cap, size_t* out_len);
+
+/* The batch form, in two calls so that the caller allocates the output
+ * between them.  Stored objects as in hdx_hash_encoded_device (value i =
+ * vals[val_off[i], +val_len[i]), key i = keys[key_off[i], +key_len[i]), any
+ * placement, keys == vals records included); m indices (1..HDX_MAX_INDICES,
+ * `specs` a HOST array); entry e = i*m + k, object-major (the reference's
+ * write order).  All other pointers are DEVICE pointers, both calls are
+ * asynchronous on `stream`, any attrs_sz up to HDX_MAX_ATTRS.
+ *
+ * Plan decodes every value under exactly the sweep's contract (a value must
+ * decode into attrs_sz - 1 attributes lying inside its bytes) and writes
+ *   attr_off[e], attr_len[e]   the indexed attribute's offset inside value i
+ *                              and its length;
+ *   entry_off[0 .. n*m]        the exclusive prefix sum of the entry sizes:
+ *                              entry e is entry_off[e+1] - entry_off[e] bytes
+ *                              at entry_off[e]; entry_off[n*m] is the total.
+ * The prefix sum takes device scratch of ~8 * (n*m / 1024) bytes from the
+ * library's per-device stream-ordered pool; if that allocation fails the call
+ * returns HDX_E_NOMEM and launches nothing.
+ *
+ * Fill writes entry e at entries + entry_off[e] (entries may have any
+ * alignment; only the entries' own bytes are written).  If entry_off[n*m] >
+ * entries_bytes it writes nothing and ORs (1u << HDX_E_NOMEM) into
+ * *status_dev.
+ *
+ * Refusals are all or nothing per object: an object whose value does not
+ * decode ((1u << HDX_E_BADENC) ORed into *status_dev), or whose key or any
+ * INDEXED attribute is a numeric of neither 0 nor 8 bytes ((1u <<
+ * HDX_E_BADSIZE); the reference asserts), gets m entries of size 0 and zero
+ * descriptors; every other object's entries are exact.  A mis-sized numeric
+ * in an attribute no index names does not matter (the reference never looks
+ * at it).  Before the device is touched: HDX_E_INVALID for m == 0, m >
+ * HDX_MAX_INDICES, attr == 0, attr >= attrs_sz, a prefix_len out of range or
+ * a NULL pointer (status_dev may be NULL); HDX_E_BADTYPE as above. */
+hdx_status hdx_index_entries_plan_device(const uint32_t* types, uint32_t attrs_sz, const uint32_t* key_len,
+                                         const uint8_t* vals, const uint64_t* val_off, const uint32_t* val_len,
+                                         uint64_t n, const hdx_index_spec* specs, uint32_t m,
+                                         uint32_t* attr_off, uint32_t* attr_len, uint64_t* entry_off,
+                                         uint32_t* status_dev, hdx_stream stream);
+hdx_status hdx_index_entries_fill_device(const uint32_t* types, uint32_t attrs_sz, const uint8_t* keys,
+                                         const uint64_t* key_off, const uint32_t* key_len, const uint8_t* vals,
+                                         const uint64_t* val_off, uint64_t n, const hdx_index_spec* specs,
+                                         uint32_t m, const uint32_t* attr_off, const uint32_t* attr_len,
+                                         const uint64_t* entry_off, uint8_t* entries, uint64_t entries_bytes,
+                                         uint32_t* status_dev, hdx_stream stream);
+/* Elements per workgroup of the plan's prefix sum (its levels change at
+ * powers of this; tests stand on them). */
+uint32_t hdx_index_scan_block(void);
+
 /* One range of a search, as range_searches() leaves it (common/range.h:40-55,
  * common/range_searches.cc:151-202): inclusive, at most one per attribute. */
 typedef struct hdx_range {
