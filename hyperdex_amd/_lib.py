@@ -97,6 +97,10 @@ SIGNATURES = [
     ("hdx_index_entries_fill_device", _i32, [_vp, _u32, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _u32, _vp, _vp, _vp,
                                              _vp, _u64, _vp, _vp]),
     ("hdx_index_scan_block", _u32, []),
+    ("hdx_passes_checks", _i32, [_vp, _u32, _vp, _sz, _vp, _vp, _vp, _u32, _vp]),
+    ("hdx_check_encoded_device", _i32, [_vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _u32, _vp, _vp, _vp,
+                                        _vp, _vp]),
+    ("hdx_check_block_objects", _u32, []),
     ("hdx_search_regions", _i32, [_vp, _vp, _u32, _vp, _vp, _vp]),
     ("hdx_search_space", _i32, [_vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp, _vp]),
     ("hdx_batcher_create", _i32, [_vp, _u32, _vp, _vp]),

@@ -1,0 +1,105 @@
+"""A search's attribute checks (common/attribute_check.cc:123-237; the table is
+restated in include/hdxhash.h).
+
+passes_checks   one object on the host CPU (hdx_passes_checks):
+                passes_attribute_checks' result, the index of the first check
+                that fails or len(checks).
+check_encoded   a batch of stored objects on the GPU (hdx_check_encoded_device):
+                what datalayer::search_iterator::valid() does per candidate
+                (daemon/datalayer_iterator.cc:792-850), plus the compacted list
+                of the objects that pass.
+"""
+import ctypes
+from typing import Sequence
+
+import numpy as np
+
+from ._lib import check, lib
+
+HDX_MAX_CHECKS = 16
+HDX_CHECK_BYTES_MAX = 1024
+HDX_CHECK_BADENC = 0xffffffff
+
+
+class _Check(ctypes.Structure):
+    """hdx_attribute_check (include/hdxhash.h)."""
+    _fields_ = [("attr", ctypes.c_uint32), ("datatype", ctypes.c_uint32), ("predicate", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32), ("value", ctypes.c_char_p), ("value_len", ctypes.c_uint64)]
+
+
+class AttributeCheck:
+    """common/attribute_check.h: the schema attribute (0 = the key), the
+    check's value and its hyperdatatype, and a HYPERPREDICATE_* value."""
+
+    def __init__(self, attr: int, value: bytes, datatype: int, predicate: int):
+        self.attr, self.value, self.datatype, self.predicate = int(attr), bytes(value), int(datatype), int(predicate)
+
+    def __repr__(self):
+        return "AttributeCheck(%d, %r, %d, %d)" % (self.attr, self.value, self.datatype, self.predicate)
+
+
+def _checks(checks: Sequence[AttributeCheck]):
+    """The C array; it refers to the checks' own bytes, which `checks` keeps alive."""
+    arr = (_Check * max(len(checks), 1))()
+    for k, ck in enumerate(checks):
+        arr[k].attr, arr[k].datatype, arr[k].predicate = ck.attr, ck.datatype, ck.predicate
+        arr[k].value, arr[k].value_len = ck.value, len(ck.value)
+    return arr
+
+
+def check_block_objects() -> int:
+    """Objects per workgroup of the check kernel (the compaction scans one count each)."""
+    return int(lib().hdx_check_block_objects())
+
+
+def passes_checks(types, key: bytes, values: Sequence[bytes], checks: Sequence[AttributeCheck]) -> int:
+    """passes_attribute_checks(schema, checks, key, value) for one object:
+    the index of the first failing check, len(checks) when all pass."""
+    t = np.ascontiguousarray(np.asarray(types, dtype=np.uint32))
+    m = len(values)
+    ptrs = (ctypes.c_char_p * max(m, 1))(*[bytes(v) for v in values])
+    lens = (ctypes.c_size_t * max(m, 1))(*[len(v) for v in values])
+    out = ctypes.c_uint32(0)
+    check(lib().hdx_passes_checks(t.ctypes.data, len(t), bytes(key), len(key), ptrs, lens, _checks(checks),
+                                  len(checks), ctypes.byref(out)))
+    return int(out.value)
+
+
+def check_encoded(types, keys, key_off, key_len, vals, val_off, val_len, checks: Sequence[AttributeCheck],
+                  want_match=True, status=None, stream=None):
+    """hdx_check_encoded_device on torch HIP tensors (stored objects as in
+    hash_encoded): returns (first_fail i32[n], match i64[count] or None).
+    first_fail holds u32 bit patterns: 0 .. len(checks), or -1
+    (HDX_CHECK_BADENC) for a value that does not decode (status: HDX_E_BADENC's
+    bit).  match: the indices with first_fail == len(checks), ascending; with
+    want_match the count is read back on `stream`, which is then waited for."""
+    import torch
+
+    from .index import _torch_stream
+
+    t = np.ascontiguousarray(np.asarray(types, dtype=np.uint32))
+    n = val_off.numel()
+    dev = val_off.device
+    for x in (keys, key_off, key_len, vals, val_off, val_len):
+        assert x.is_cuda and x.is_contiguous()
+    assert val_len.numel() == n and key_len.numel() == n and key_off.numel() == n
+    s = _torch_stream(stream, dev)
+    with torch.cuda.stream(s):
+        first_fail = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        match = torch.empty(max(n, 1), dtype=torch.int64, device=dev) if want_match else None
+        count = torch.empty(1, dtype=torch.int64, device=dev) if want_match else None
+    # tensors without elements have no address: first_fail stands in for them; nothing reads it when n == 0
+    keys, key_off, key_len, vals, val_off, val_len = [x if x.numel() else first_fail
+                                                      for x in (keys, key_off, key_len, vals, val_off, val_len)]
+    check(lib().hdx_check_encoded_device(
+        t.ctypes.data, len(t), keys.data_ptr(), key_off.data_ptr(), key_len.data_ptr(), vals.data_ptr(),
+        val_off.data_ptr(), val_len.data_ptr(), n, _checks(checks), len(checks), first_fail.data_ptr(),
+        match.data_ptr() if want_match else None, count.data_ptr() if want_match else None,
+        status.data_ptr() if status is not None else None, s.cuda_stream))
+    if not want_match:
+        return first_fail[:n], None
+    with torch.cuda.stream(s):
+        host = torch.empty(1, dtype=torch.int64, pin_memory=True)
+        host.copy_(count, non_blocking=True)
+        s.synchronize()
+    return first_fail[:n], match[:int(host.item())]

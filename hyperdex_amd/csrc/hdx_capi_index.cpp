@@ -190,6 +190,47 @@ HDX_EXPORT hdx_status hdx_index_entries_fill_device(const uint32_t* types, uint3
     return HDX_OK;
 }
 
+// ---- a search's attribute checks over stored objects (hdx_checks.hip) ------
+
+HDX_EXPORT uint32_t hdx_check_block_objects(void) { return kCheckBlock; }
+
+HDX_EXPORT hdx_status hdx_check_encoded_device(const uint32_t* types, uint32_t attrs_sz, const uint8_t* keys,
+                                               const uint64_t* key_off, const uint32_t* key_len,
+                                               const uint8_t* vals, const uint64_t* val_off,
+                                               const uint32_t* val_len, uint64_t n,
+                                               const hdx_attribute_check* checks, uint32_t c,
+                                               uint32_t* first_fail, uint64_t* match, uint64_t* match_count,
+                                               uint32_t* status_dev, hdx_stream stream) {
+    CheckArgs a{};
+    hdx_status st = compile_checks(types, attrs_sz, checks, c, HDX_CHECK_BYTES_MAX, a.op);
+    if (st != HDX_OK) return st;
+    if (!keys || !key_off || !key_len || !vals || !val_off || !val_len || !first_fail)
+        return fail(HDX_E_INVALID, "NULL device pointer");
+    if (match && !match_count) return fail(HDX_E_INVALID, "match without match_count");
+    if ((st = bind_device(-1)) != HDX_OK) return st;
+    // the STRING comparisons' constants, each at its op's 8-byte-aligned offset (a.konst is zeroed)
+    for (uint32_t k = 0; k < c; ++k)
+        if (a.op[k].op != OP_NEVER && a.op[k].op < OP_LEN_EQ && a.op[k].family == FAM_STRING && a.op[k].klen)
+            std::memcpy(reinterpret_cast<uint8_t*>(a.konst) + a.op[k].koff, checks[k].value, a.op[k].klen);
+    a.keys = keys;
+    a.key_off = key_off;
+    a.key_len = key_len;
+    a.vals = vals;
+    a.val_off = val_off;
+    a.val_len = val_len;
+    a.first_fail = first_fail;
+    a.match = match;
+    a.match_count = match_count;
+    a.status = status_dev;
+    a.n = n;
+    a.A = attrs_sz;
+    a.c = c;
+    bool no_scratch = false;
+    HIP_TRY(launch_check_encoded(a, (hipStream_t)stream, &no_scratch));
+    if (no_scratch) return fail(HDX_E_NOMEM, "compaction scratch for %llu objects", (unsigned long long)n);
+    return HDX_OK;
+}
+
 HDX_EXPORT hdx_status hdx_search_regions(hdx_region_table t, const hdx_range* ranges, uint32_t nranges,
                                          const uint8_t* has_replicas, uint8_t* include, int* cleared) {
     if (!t || !cleared || (nranges && !ranges) || (t->R && !include))

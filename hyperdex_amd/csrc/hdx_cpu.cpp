@@ -301,3 +301,63 @@ HDX_EXPORT hdx_status hdx_index_entry(const hdx_index_spec* spec, uint32_t key_t
     }
     return HDX_OK;
 }
+
+// ---- one object against a search's attribute checks (include/hdxhash.h) ----
+
+namespace {
+
+// passes_attribute_check (common/attribute_check.cc:141-199) past what
+// compile_checks decided: validate(v), then the comparison.  k: the check's
+// own bytes (a STRING comparison reads them in place).
+bool check_passes(const CheckOp& o, const uint8_t* k, const uint8_t* v, size_t len) {
+    if (o.op == OP_NEVER) return false;
+    if (o.op >= OP_LEN_EQ) {  // :178-199, T == STRING: length(v) = its size
+        const int64_t L = (int64_t)len, tmp = (int64_t)o.imm;
+        return o.op == OP_LEN_EQ ? L == tmp : o.op == OP_LEN_LE ? L <= tmp : L >= tmp;
+    }
+    int cmp;
+    if (o.family == FAM_STRING) {  // datatype_string.cc:263-285; memcmp compares unsigned bytes
+        const size_t m = o.klen < len ? o.klen : len;
+        cmp = m ? memcmp(k, v, m) : 0;
+        if (cmp == 0) cmp = o.klen < len ? -1 : o.klen > len ? 1 : 0;
+    } else {
+        if (len != 0 && len != 8) return false;  // :141 validate(v): fails every check on it
+        const uint64_t vb = len ? cpu::le64(v) : 0;  // an empty value is 0 / 0.0
+        if (o.family == FAM_INT64) {  // datatype_int64.cc, datatype_timestamp.cc:268-285
+            const int64_t a = (int64_t)o.imm, b = (int64_t)vb;
+            cmp = a < b ? -1 : a > b ? 1 : 0;
+        } else {  // datatype_float.cc:256-273: a NaN on either side gives 0
+            double a, b;
+            memcpy(&a, &o.imm, 8);
+            memcpy(&b, &vb, 8);
+            cmp = a < b ? -1 : a > b ? 1 : 0;
+        }
+    }
+    return check_relation(o.op, cmp);
+}
+
+}  // namespace
+
+// passes_attribute_checks, common/attribute_check.cc:209-237
+HDX_EXPORT hdx_status hdx_passes_checks(const uint32_t* types, uint32_t attrs_sz, const uint8_t* key,
+                                        size_t key_len, const uint8_t* const* values, const size_t* value_lens,
+                                        const hdx_attribute_check* checks, uint32_t c, uint32_t* first_fail) {
+    CheckOp ops[HDX_MAX_CHECKS];
+    const hdx_status st = compile_checks(types, attrs_sz, checks, c, UINT64_MAX, ops);
+    if (st != HDX_OK) return st;
+    if (!first_fail || (!key && key_len) || (attrs_sz > 1 && (!values || !value_lens)))
+        return fail(HDX_E_INVALID, "NULL pointer");
+    for (uint32_t i = 0; i < c; ++i)
+        if (ops[i].op != OP_NEVER && ops[i].attr && !values[ops[i].attr - 1] && value_lens[ops[i].attr - 1])
+            return fail(HDX_E_INVALID, "value %u is NULL", ops[i].attr - 1);
+    uint32_t i = 0;
+    for (; i < c; ++i) {
+        const CheckOp& o = ops[i];
+        const bool on_key = o.attr == 0;
+        if (!check_passes(o, checks[i].value, on_key ? key : values[o.attr - 1],
+                          on_key ? key_len : value_lens[o.attr - 1]))
+            break;
+    }
+    *first_fail = i;
+    return HDX_OK;
+}

@@ -69,4 +69,126 @@ inline uint64_t entry_encoded_size(uint32_t enc, uint64_t len) {
 // Sets the calling thread's hdx_last_error() text and returns s.
 hdx_status fail(hdx_status s, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 
+// ---- a search's attribute checks (common/attribute_check.cc:123-237) --------
+//
+// One compiled form for the per-object CPU path (hdx_cpu.cpp) and the device
+// launcher (hdx_capi_index.cpp, hdx_checks.hip): op k stands for checks[k].
+// Everything of passes_attribute_check that does not depend on the object is
+// decided by compile_checks; what is left per object is the attribute's own
+// validate() (:141) and one comparison.
+enum : uint8_t { OP_NEVER = 0, OP_EQ, OP_LT, OP_LE, OP_GE, OP_GT, OP_LEN_EQ, OP_LEN_LE, OP_LEN_GE };
+enum : uint8_t { FAM_STRING = 0, FAM_INT64 = 1, FAM_FLOAT = 2 };
+struct CheckOp {
+    uint16_t attr;   // 0: the key; 0 also with OP_NEVER, which reads nothing
+    uint8_t op, family;
+    uint32_t klen;   // FAM_STRING comparisons: the constant's length
+    uint32_t koff;   // ... and its 8-byte-aligned offset in the packed constants (pack_check_constants)
+    uint32_t pad_;
+    uint64_t imm;    // numeric comparisons: k's little-endian bits (empty: 0); OP_LEN_*: tmp
+};
+// Room for the packed STRING constants: each starts 8-byte aligned and is zero-padded to 8.
+constexpr uint32_t kCheckConstBytes = HDX_CHECK_BYTES_MAX + 8 * HDX_MAX_CHECKS;
+
+// FAM_* of an attribute type the checks are built for, -1 for every other
+// type (document_check, container length / contains: out of scope).
+inline int check_family(uint32_t type) {
+    const int c = type_code(type);
+    if (c == (int)CODE_STRING) return FAM_STRING;
+    if (c == (int)CODE_INT64) return FAM_INT64;
+    if (c == (int)CODE_FLOAT) return FAM_FLOAT;
+    if (c >= (int)CODE_TS_SECOND && c <= (int)CODE_TS_MONTH) return FAM_INT64;  // datatype_timestamp.cc:268-285
+    return -1;
+}
+
+// The argument checks of both forms, then ops[0..c).  max_bytes: the cap on
+// the sum of the checks' value_len (the device form's HDX_CHECK_BYTES_MAX: its
+// constants travel in the kernel arguments; the CPU form reads them in place
+// and has none).
+inline hdx_status compile_checks(const uint32_t* types, uint32_t attrs_sz, const hdx_attribute_check* checks,
+                                 uint32_t c, uint64_t max_bytes, CheckOp* ops) {
+    if (!types) return fail(HDX_E_INVALID, "types is NULL");
+    if (attrs_sz == 0 || attrs_sz > HDX_MAX_ATTRS)
+        return fail(HDX_E_INVALID, "attrs_sz=%u outside [1, %d]", attrs_sz, HDX_MAX_ATTRS);
+    if (c > HDX_MAX_CHECKS) return fail(HDX_E_INVALID, "c=%u above %d", c, HDX_MAX_CHECKS);
+    if (c && !checks) return fail(HDX_E_INVALID, "checks is NULL");
+    uint64_t bytes = 0;
+    for (uint32_t i = 0; i < c; ++i) {
+        if (!checks[i].value && checks[i].value_len) return fail(HDX_E_INVALID, "check %u: value is NULL", i);
+        if (checks[i].value_len > max_bytes - bytes)
+            return fail(HDX_E_INVALID, "the checks' values exceed %llu bytes", (unsigned long long)max_bytes);
+        bytes += checks[i].value_len;
+    }
+    uint32_t koff = 0;
+    for (uint32_t i = 0; i < c; ++i) {
+        const hdx_attribute_check& ck = checks[i];
+        CheckOp& o = ops[i];
+        o = CheckOp{};
+        if (ck.attr >= attrs_sz) continue;  // :217-220: fails at i
+        const uint32_t T = types[ck.attr], D = ck.datatype;
+        const int fam = check_family(T);
+        if (fam < 0)
+            return fail(HDX_E_BADTYPE, "check %u: attribute %u of hyperdatatype %u (only STRING, INT64, FLOAT, TIMESTAMP_*)",
+                        i, ck.attr, T);
+        if (ck.predicate == 9733 && T == 9217 && D == 9217)  // :174-177, the one case that runs regex_match
+            return fail(HDX_E_BADTYPE, "check %u: REGEX on a STRING attribute is not supported", i);
+        // :128-134 lookup(D) == NULL -> false.  A container, document or macaroon D is false too,
+        // whichever way its validate(k) goes: T is primitive here, so T == D (:155-173) fails, the
+        // LENGTH forms want D == INT64 (:182-199), REGEX wants D == STRING (:175), and a primitive
+        // has_contains() is false (:201).  So nothing of those types is implemented.
+        const int dfam = check_family(D);
+        if (dfam < 0) continue;
+        // :142 validate(k) under D
+        if (dfam != (int)FAM_STRING && ck.value_len != 0 && ck.value_len != 8) continue;
+        uint8_t op = OP_NEVER;
+        switch (ck.predicate) {
+            case 9729: op = OP_EQ; break;
+            case 9738: op = OP_LT; break;
+            case 9730: op = OP_LE; break;
+            case 9731: op = OP_GE; break;
+            case 9739: op = OP_GT; break;
+            case 9734: op = OP_LEN_EQ; break;
+            case 9732:  // CONTAINS_LESS_THAN shares LENGTH_LESS_EQUAL's code (:185-192)
+            case 9735: op = OP_LEN_LE; break;
+            case 9736: op = OP_LEN_GE; break;
+            default: break;  // FAIL, CONTAINS (no primitive has_contains()), REGEX left over, unknown values
+        }
+        if (op == OP_NEVER) continue;
+        if (op >= OP_LEN_EQ) {
+            // :179-184: D == INT64 exactly, has_length() (of these types only STRING)
+            if (D != 9218 || fam != (int)FAM_STRING) continue;
+            uint64_t tmp = 0;  // the first min(len(k), 8) bytes, little-endian, zero-padded
+            for (uint64_t b = 0; b < ck.value_len && b < 8; ++b) tmp |= (uint64_t)ck.value[b] << (8 * b);
+            o.imm = tmp;
+        } else {
+            if (T != D) continue;  // an exact type match: two timestamp granularities differ
+            if (fam == (int)FAM_STRING) {
+                o.klen = (uint32_t)ck.value_len;
+                o.koff = koff;
+                koff += ((uint32_t)ck.value_len + 7u) & ~7u;
+            } else {
+                for (uint64_t b = 0; b < ck.value_len; ++b) o.imm |= (uint64_t)ck.value[b] << (8 * b);
+            }
+        }
+        o.attr = (uint16_t)ck.attr;
+        o.op = op;
+        o.family = (uint8_t)fam;
+    }
+    return HDX_OK;
+}
+
+// The relation a comparing op asks of cmp = compare(k, v), the check's value on the left (:154-173).
+// Host and device: the kernel applies the same table.
+#ifdef __HIPCC__
+__host__ __device__
+#endif
+inline bool check_relation(uint8_t op, int cmp) {
+    switch (op) {
+        case OP_EQ: return cmp == 0;  // k == v bytewise implies compare == 0 in every family
+        case OP_LT: return cmp > 0;
+        case OP_LE: return cmp >= 0;
+        case OP_GE: return cmp <= 0;
+        default: return cmp < 0;      // OP_GT
+    }
+}
+
 }  // namespace hdx

@@ -6,10 +6,11 @@
 // include/hdxhash.h).  Entry e = i*m + k, object-major.
 //
 //   plan  index_plan_kernel: a lane per object walks its value's [u32 BE len]
-//         chain exactly as sweep_wide_walk_kernel does (hdx_wide.hip: the full
-//         walk, so its verdict is the sweep's), keeps the descriptors of the
-//         indexed attributes in LDS, and the workgroup then stores attr_off,
-//         attr_len and the entry sizes of its objects coalesced.
+//         chain (value_walk, hdx_value_walk.h: the full walk, as
+//         sweep_wide_walk_kernel's, so its verdict is the sweep's), keeps the
+//         descriptors of the indexed attributes in LDS, and the workgroup then
+//         stores attr_off, attr_len and the entry sizes of its objects
+//         coalesced.
 //   scan  the exclusive prefix sum of the n*m + 1 sizes (the last one is 0,
 //         so entry_off[n*m] is the total), reduce-then-scan over separate
 //         launches: index_scan_sums_kernel (one sum per kIndexScanBlock
@@ -35,6 +36,7 @@
 
 #include "hdx_device_hash.h"
 #include "hdx_internal.h"
+#include "hdx_value_walk.h"
 
 namespace hdx {
 
@@ -78,31 +80,15 @@ __global__ void __launch_bounds__(256) index_plan_kernel(const IndexEntriesArgs 
         const uint32_t A = a.A;
         const uint8_t* v = a.vals + a.val_off[i];
         const uint32_t vlen = a.val_len[i];
-        // decode_value, daemon/datalayer_encodings.cc:174-213, under the
-        // sweep's contract: the header, count == A - 1, every prefix and
-        // every attribute inside the value
-        bool ok = vlen >= 10;
-        if (ok) ok = (__builtin_bswap32(*(ie_gu32_ptr)(v + 6)) & 0xffffu) == A - 1;  // the u16 at bytes 8..9
-        uint32_t pos = 10;  // pos <= vlen throughout
-        for (uint32_t j = 1; ok && j < A; ++j) {
-            if (vlen - pos < 4) {
-                ok = false;
-                break;
-            }
-            const uint32_t L = __builtin_bswap32(*(ie_gu32_ptr)(v + pos));
-            pos += 4;
-            if (L > vlen - pos) {
-                ok = false;
-                break;
-            }
+        // decode_value under the sweep's contract (hdx_value_walk.h)
+        const bool ok = value_walk(v, vlen, A, [&](uint32_t j, uint32_t pos, uint32_t L) {
             for (uint32_t k = 0; k < m; ++k)  // uniform: the specs are kernel arguments
                 if (a.attr[k] == j) {
                     s_off[tid * m + k] = pos;
                     s_len[tid * m + k] = L;
                     if (a.enc[k] != ENC_STRING && L != 0 && L != 8) badsize = true;
                 }
-            pos += L;
-        }
+        });
         badenc = !ok;
         const uint32_t kl = a.key_len[i];
         if (a.key_enc != ENC_STRING && kl != 0 && kl != 8) badsize = true;
@@ -201,6 +187,8 @@ __global__ void __launch_bounds__(kScanThreads) index_scan_block_kernel(uint64_t
     }
 }
 
+}  // namespace
+
 hipError_t scan_exclusive(uint64_t* data, uint64_t N, uint64_t* scratch, hipStream_t stream) {
     const uint64_t blocks = (N + kIndexScanBlock - 1) / kIndexScanBlock;
     if (blocks > 0x7fffffffULL) return hipErrorInvalidValue;
@@ -228,6 +216,8 @@ uint64_t scan_scratch_words(uint64_t N) {
     }
     return words;
 }
+
+namespace {
 
 // ---- fill -----------------------------------------------------------------
 

@@ -256,6 +256,37 @@ struct IndexEntriesArgs {
 // that allocation fails nothing is launched and *no_scratch is set.
 hipError_t launch_index_entries_plan(const IndexEntriesArgs& a, hipStream_t stream, bool* no_scratch);
 hipError_t launch_index_entries_fill(const IndexEntriesArgs& a, hipStream_t stream);
+// The reduce-then-scan itself (hdx_index_entries.hip): the exclusive prefix
+// sum of data[0..N) in place, over separate launches; scratch holds
+// scan_scratch_words(N) u64 of block sums (none up to kIndexScanBlock).
+hipError_t scan_exclusive(uint64_t* data, uint64_t N, uint64_t* scratch, hipStream_t stream);
+uint64_t scan_scratch_words(uint64_t N);
+
+// A search's attribute checks over stored objects (hdx_checks.hip): the ops
+// of compile_checks (hdx_host_common.h) and their STRING constants, packed
+// at op[k].koff, travel by value.
+constexpr uint32_t kCheckBlock = 256;  // objects per workgroup of both kernels
+struct CheckArgs {
+    const uint8_t* keys;
+    const uint64_t* key_off;
+    const uint32_t* key_len;
+    const uint8_t* vals;
+    const uint64_t* val_off;
+    const uint32_t* val_len;
+    uint32_t* first_fail;  // [n]
+    uint64_t* match;       // [n] or NULL: no compaction
+    uint64_t* match_count;
+    uint32_t* status;      // may be NULL
+    uint64_t n;
+    uint32_t A, c;
+    CheckOp op[HDX_MAX_CHECKS];
+    uint64_t konst[kCheckConstBytes / 8];
+};
+// check_kernel (the walk and the ops, a lane per object); with a.match also
+// one pass count per workgroup, their scan (scan_exclusive) and
+// check_compact_kernel.  The counts come from the library's stream-ordered
+// pool; if that allocation fails nothing is launched and *no_scratch is set.
+hipError_t launch_check_encoded(const CheckArgs& a, hipStream_t stream, bool* no_scratch);
 // hdx_regions.hip: the library's per-device memory pool for stream-ordered
 // scratch (the regions' coordinate chunks and this scan's block sums), on the
 // calling thread's current device.

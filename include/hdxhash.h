@@ -472,6 +472,100 @@ hdx_status hdx_index_entries_fill_device(const uint32_t* types, uint32_t attrs_s
  * powers of this; tests stand on them). */
 uint32_t hdx_index_scan_block(void);
 
+/* ---- a search's attribute checks over stored objects ---------------------- */
+
+/* What datalayer::search_iterator::valid() (daemon/datalayer_iterator.cc:
+ * 792-850) does per candidate object behind search, count, group_del and
+ * sorted_search: decode_value, then passes_attribute_checks(sc, checks, key,
+ * value) (common/attribute_check.cc:209-237), which returns the index of the
+ * FIRST check that fails, or c when all pass.  A check whose attr >=
+ * attrs_sz fails; attr == 0 tests the key under types[0], attr > 0 tests
+ * value[attr-1] under types[attr].  One check (passes_attribute_check,
+ * :123-207), with T = types[attr], D = check.datatype, v the attribute's
+ * bytes, k the check's bytes (predicate: enum hyperpredicate's values,
+ * include/hyperdex.h:108-119):
+ *   - false when D is not a type hdx_schema_check accepts (:128-134);
+ *   - false when v does not validate under T or k under D (:141-145): STRING
+ *     always validates, INT64 / FLOAT / TIMESTAMP_* iff the size is 0 or 8 —
+ *     so a stored numeric of 1-7 or 9 bytes fails every check on it, with no
+ *     HDX_E_BADSIZE (the reference does not assert here either);
+ *   - FAIL                                  false
+ *     EQUALS                                T == D && compare(k, v) == 0
+ *     LESS_THAN / LESS_EQUAL /              T == D && compare(k, v) > 0 / >= 0 /
+ *     GREATER_EQUAL / GREATER_THAN                                  <= 0 / < 0
+ *     LENGTH_EQUALS / LENGTH_LESS_EQUAL /   D == INT64 && T == STRING &&
+ *     LENGTH_GREATER_EQUAL                  (int64)len(v) == / <= / >= tmp, tmp = the first
+ *                                           min(len(k), 8) bytes of k, little-endian, zero-padded
+ *     CONTAINS_LESS_THAN                    as LENGTH_LESS_EQUAL (:185-192)
+ *     CONTAINS, any other value             false for these attribute types
+ *   compare, the CHECK's value on the left: STRING memcmp over the shorter
+ *   length (unsigned bytes), then the lengths (datatype_string.cc:263-285);
+ *   INT64 and each TIMESTAMP_* signed 64-bit little-endian values, empty = 0;
+ *   FLOAT double < and >, empty = 0.0 — a NaN on either side compares 0, so it
+ *   EQUALS everything and passes <= and >=; -0.0 equals 0.0.  T == D is exact:
+ *   two timestamp granularities are different types.
+ * Out of scope, HDX_E_BADTYPE before anything runs, in both forms: a check
+ * with attr < attrs_sz whose attribute type is not STRING, INT64, FLOAT or
+ * TIMESTAMP_* (the reference runs document_check, container length or
+ * contains); REGEX where T == D == STRING (regex_match).  REGEX otherwise,
+ * and any D on a primitive attribute, is simply false.  Also out of scope:
+ * validate_attribute_checks, a host-resident (_host) pipeline, the device
+ * set, check constants resident on the device. */
+#define HDX_MAX_CHECKS 16
+#define HDX_CHECK_BYTES_MAX 1024      /* sum of the checks' value_len (device form) */
+#define HDX_CHECK_BADENC 0xffffffffu
+typedef struct hdx_attribute_check {
+    uint32_t attr, datatype, predicate, reserved;
+    const uint8_t* value;             /* host bytes */
+    uint64_t value_len;
+} hdx_attribute_check;
+
+/* One object on the host CPU: no device, no allocation.  *first_fail =
+ * passes_attribute_checks' result, in [0, c].  values[k] / value_lens[k] are
+ * attribute k+1, k in [0, attrs_sz-1).  HDX_E_INVALID for a NULL pointer or
+ * c > HDX_MAX_CHECKS, HDX_E_BADTYPE as above; *first_fail is then untouched.
+ * The checks' values may have any size here (HDX_CHECK_BYTES_MAX is the
+ * device form's). */
+hdx_status hdx_passes_checks(const uint32_t* types, uint32_t attrs_sz,
+                             const uint8_t* key, size_t key_len,
+                             const uint8_t* const* values, const size_t* value_lens,
+                             const hdx_attribute_check* checks, uint32_t c, uint32_t* first_fail);
+
+/* The batch form over stored objects as in hdx_hash_encoded_device (any
+ * placement and alignment, keys == vals records included; any attrs_sz up to
+ * HDX_MAX_ATTRS).  `types` and `checks` (with their values) are HOST memory,
+ * every other pointer is a DEVICE pointer; asynchronous on `stream`.
+ *   first_fail[i]   in [0, c]; HDX_CHECK_BADENC for a value that does not
+ *                   decode under exactly the sweep's contract (count ==
+ *                   attrs_sz - 1, every prefix and attribute inside the
+ *                   value), with (1u << HDX_E_BADENC) ORed into *status_dev
+ *                   (may be NULL).  The reference's iterator stops the whole
+ *                   search with an error at such an object; the batch reports
+ *                   the object and goes on.
+ *   match           (may be NULL) match[0 .. *match_count) = the indices i
+ *                   with first_fail[i] == c, ascending; nothing is written
+ *                   beyond that.  Capacity n.
+ *   match_count     one u64, required iff match != NULL.
+ * c == 0 is legal: every decodable object matches.  Before the device is
+ * touched: HDX_E_INVALID for a NULL pointer, c > HDX_MAX_CHECKS, more than
+ * HDX_CHECK_BYTES_MAX bytes of check values, or match without match_count;
+ * HDX_E_BADTYPE as above.  HDX_E_DEVICE without a device.  The check values
+ * travel in the kernel arguments (no allocation or copy per call for them:
+ * hence the two caps).  With match, the compaction takes ~8 * (n / 256) bytes
+ * from the library's per-device stream-ordered pool; if that fails nothing is
+ * launched and the call returns HDX_E_NOMEM.  No kernel waits on another
+ * workgroup, so match's order never varies. */
+hdx_status hdx_check_encoded_device(const uint32_t* types, uint32_t attrs_sz,
+                                    const uint8_t* keys, const uint64_t* key_off, const uint32_t* key_len,
+                                    const uint8_t* vals, const uint64_t* val_off, const uint32_t* val_len,
+                                    uint64_t n, const hdx_attribute_check* checks, uint32_t c,
+                                    uint32_t* first_fail, uint64_t* match, uint64_t* match_count,
+                                    uint32_t* status_dev, hdx_stream stream);
+/* Objects per workgroup of the check kernel: the compaction scans one count
+ * per workgroup, so its scan takes a second level above this times
+ * hdx_index_scan_block() objects (tests stand on it). */
+uint32_t hdx_check_block_objects(void);
+
 /* One range of a search, as range_searches() leaves it (common/range.h:40-55,
  * common/range_searches.cc:151-202): inclusive, at most one per attribute. */
 typedef struct hdx_range {
