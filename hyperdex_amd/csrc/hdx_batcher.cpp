@@ -243,18 +243,11 @@ hipError_t ship(hdx_batcher_s* b, Slot& s) {
     if (!b->tables.empty() && b->tables.size() <= kMaxSweepTables && b->A <= 128) {
         // one launch: hash + every table's lookup_region (hash_regroup_regions_kernel)
         a.T = (uint32_t)b->tables.size();
+        // (hdx_batcher_create took only tables of this device, so no view here
+        // uploads a replica; region_view fails for no other reason)
         for (uint32_t t = 0; t < a.T; ++t) {
-            const hdx_region_table tb = b->tables[t];
-            a.t[t].index = tb->d_index;
-            a.t[t].lower = tb->d_lower;
-            a.t[t].upper = tb->d_upper;
-            a.t[t].ids = tb->d_ids;
-            a.t[t].out = s.d_out + region_base + (size_t)t * s.cap_obj;
-            a.t[t].W = tb->W;
-            a.t[t].D = tb->D;
-            a.t[t].R = tb->R;
-            a.t[t].index_words = tb->index_words;
-            std::memcpy(a.t[t].attrs, tb->attrs, sizeof a.t[t].attrs);
+            uint64_t* ids = s.d_out + region_base + (size_t)t * s.cap_obj;
+            if (fill_sweep_table(a.t[t], b->tables[t], b->device, ids) != HDX_OK) return hipErrorInvalidDevice;
         }
         SHIP_TRY(launch_hash_batch_regions(a, s.stream));
     } else {
@@ -269,18 +262,8 @@ hipError_t ship(hdx_batcher_s* b, Slot& s) {
         r.out_stride = s.cap_obj;
         r.A = b->A;
         r.T = (uint32_t)b->tables.size();
-        for (uint32_t t = 0; t < r.T; ++t) {
-            const hdx_region_table tb = b->tables[t];
-            r.t[t].lower = tb->d_lower;
-            r.t[t].upper = tb->d_upper;
-            r.t[t].ids = tb->d_ids;
-            r.t[t].index = tb->d_index;
-            r.t[t].W = tb->W;
-            r.t[t].index_words = tb->index_words;
-            r.t[t].D = tb->D;
-            r.t[t].R = tb->R;
-            std::memcpy(r.t[t].attrs, tb->attrs, sizeof r.t[t].attrs);
-        }
+        for (uint32_t t = 0; t < r.T; ++t)
+            if (region_view(b->tables[t], b->device, r.t[t]) != HDX_OK) return hipErrorInvalidDevice;
         SHIP_TRY(launch_lookup_regions_multi(r, s.stream));
     }
     if (dev) {
@@ -463,10 +446,10 @@ HDX_EXPORT hdx_status hdx_batcher_create(const uint32_t* types, uint32_t attrs_s
             delete b;
             return fail(HDX_E_INVALID, "tables[%u] is NULL", t);
         }
-        if (c.tables[t]->device != dev) {
+        if (c.tables[t]->home.device != dev) {
             delete b;
             return fail(HDX_E_INVALID, "tables[%u] lives on device %d, batcher on %d", t,
-                        c.tables[t]->device, dev);
+                        c.tables[t]->home.device, dev);
         }
         for (uint32_t d = 0; d < c.tables[t]->D; ++d)
             if (c.tables[t]->attrs[d] >= attrs_sz) {

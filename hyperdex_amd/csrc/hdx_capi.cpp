@@ -381,44 +381,60 @@ HDX_EXPORT hdx_status hdx_hash_batch_device(const uint32_t* types, uint32_t attr
 }
 
 namespace hdx {
-hdx_status fill_sweep_table(SweepTable& st, hdx_region_table_s* t, int dev, uint64_t* out) {
-    st = SweepTable{};
-    st.lower = t->d_lower;
-    st.upper = t->d_upper;
-    st.ids = t->d_ids;
-    st.index = t->d_index;
-    if (dev != t->device) {
-        std::lock_guard<std::mutex> lk(t->rep_mu);
-        const hdx_region_table_s::Replica* r = nullptr;
+using TableCopy = hdx_region_table_s::Copy;
+
+static void free_table_copy(const TableCopy& c) {
+    (void)hipFree(c.lower);
+    (void)hipFree(c.upper);
+    (void)hipFree(c.ids);
+    (void)hipFree(c.index);
+}
+
+// The table's host arrays on the calling thread's current device (c.device):
+// HDX_E_NOMEM for a failed allocation, HDX_E_DEVICE for a failed copy, with
+// whatever was allocated left in c for free_table_copy.
+static hdx_status upload_table_copy(const hdx_region_table_s* t, TableCopy& c) {
+    const auto up = [](uint64_t** dev, const std::vector<uint64_t>& host, size_t pad) {
+        if (hipMalloc((void**)dev, host.size() * 8 + pad) != hipSuccess) return HDX_E_NOMEM;
+        if (!host.empty() && hipMemcpy(*dev, host.data(), host.size() * 8, hipMemcpyHostToDevice) != hipSuccess)
+            return HDX_E_DEVICE;
+        return HDX_OK;
+    };
+    hdx_status st;
+    if ((st = up(&c.lower, t->h_lower, 8)) != HDX_OK || (st = up(&c.upper, t->h_upper, 8)) != HDX_OK ||
+        (st = up(&c.ids, t->h_ids, 8)) != HDX_OK)
+        return st;
+    return t->h_index.empty() ? HDX_OK : up(&c.index, t->h_index, 0);  // no index: lookups scan
+}
+
+hdx_status region_view(hdx_region_table_s* t, int dev, RegionView& v) {
+    const TableCopy* c = &t->home;
+    std::unique_lock<std::mutex> lk(t->rep_mu, std::defer_lock);
+    if (dev != t->home.device) {
+        lk.lock();
+        c = nullptr;
         for (const auto& x : t->replicas)
-            if (x.device == dev) r = &x;
-        if (!r) {
-            hdx_region_table_s::Replica c{dev, nullptr, nullptr, nullptr, nullptr};
-            auto up = [](uint64_t** d, const std::vector<uint64_t>& h, size_t extra) {
-                if (hipMalloc((void**)d, h.size() * 8 + extra) != hipSuccess) return false;
-                return h.empty() || hipMemcpy(*d, h.data(), h.size() * 8, hipMemcpyHostToDevice) == hipSuccess;
-            };
-            const bool ok = up(&c.lower, t->h_lower, 8) && up(&c.upper, t->h_upper, 8) && up(&c.ids, t->h_ids, 8) &&
-                            (t->h_index.empty() || !t->d_index || up(&c.index, t->h_index, 0));
-            if (!ok) {
+            if (x.device == dev) c = &x;
+        if (!c) {
+            TableCopy up{dev, nullptr, nullptr, nullptr, nullptr};
+            if (upload_table_copy(t, up) != HDX_OK) {
                 (void)hipGetLastError();
-                (void)hipFree(c.lower); (void)hipFree(c.upper); (void)hipFree(c.ids); (void)hipFree(c.index);
+                free_table_copy(up);
                 return fail(HDX_E_NOMEM, "region table replica on device %d", dev);
             }
-            t->replicas.push_back(c);
-            r = &t->replicas.back();
+            t->replicas.push_back(up);
+            c = &t->replicas.back();
         }
-        st.lower = r->lower;
-        st.upper = r->upper;
-        st.ids = r->ids;
-        st.index = r->index;
     }
-    st.out = out;
-    st.W = t->W;
-    st.D = t->D;
-    st.R = t->R;
-    st.index_words = t->index_words;
-    std::memcpy(st.attrs, t->attrs, sizeof st.attrs);
+    v.index = c->index;
+    v.lower = c->lower;
+    v.upper = c->upper;
+    v.ids = c->ids;
+    v.W = t->W;
+    v.D = t->D;
+    v.R = t->R;
+    v.index_words = t->index_words;
+    std::memcpy(v.attrs, t->attrs, sizeof v.attrs);
     return HDX_OK;
 }
 }  // namespace hdx
@@ -666,40 +682,22 @@ HDX_EXPORT hdx_status hdx_region_table_create(uint32_t dims, uint32_t regions, c
     hdx_status st = bind_device(-1);
     if (st != HDX_OK) return st;
     hdx_region_table t = new hdx_region_table_s();
-    t->device = t_state.device;
+    t->home.device = t_state.device;
     t->D = dims;
     t->R = regions;
     std::memcpy(t->attrs, attrs, dims * sizeof(uint16_t));
     t->h_lower.assign(lower, lower + (size_t)regions * dims);
     t->h_upper.assign(upper, upper + (size_t)regions * dims);
     t->h_ids.assign(ids, ids + regions);
-    const size_t box = (size_t)regions * dims * 8;
-    if (hipMalloc((void**)&t->d_lower, box + 8) != hipSuccess ||
-        hipMalloc((void**)&t->d_upper, box + 8) != hipSuccess ||
-        hipMalloc((void**)&t->d_ids, (size_t)regions * 8 + 8) != hipSuccess) {
+    // the interval index (hdx_region_index.h) for tables of up to 256 regions
+    region_index_build(dims, regions, lower, upper, t->h_index, t->W);
+    if (region_index_disabled()) t->h_index.clear();
+    t->index_words = (uint32_t)t->h_index.size();
+    if ((st = upload_table_copy(t, t->home)) != HDX_OK) {
         (void)hipGetLastError();
         hdx_region_table_destroy(t);
-        return fail(HDX_E_NOMEM, "region table of %u regions", regions);
-    }
-    if (regions &&
-        (hipMemcpy(t->d_lower, lower, box, hipMemcpyHostToDevice) != hipSuccess ||
-         hipMemcpy(t->d_upper, upper, box, hipMemcpyHostToDevice) != hipSuccess ||
-         hipMemcpy(t->d_ids, ids, (size_t)regions * 8, hipMemcpyHostToDevice) != hipSuccess)) {
-        hdx_region_table_destroy(t);
-        return fail(HDX_E_DEVICE, "region table upload failed");
-    }
-    // the interval index (hdx_regions.hip) for tables of up to 256 regions
-    std::vector<uint64_t> index;
-    region_index_build(dims, regions, lower, upper, index, t->W);
-    if (!index.empty() && !region_index_disabled()) {
-        t->h_index = index;
-        t->index_words = (uint32_t)index.size();
-        if (hipMalloc((void**)&t->d_index, index.size() * 8) != hipSuccess ||
-            hipMemcpy(t->d_index, index.data(), index.size() * 8, hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipGetLastError();
-            hdx_region_table_destroy(t);
-            return fail(HDX_E_DEVICE, "region index upload failed");
-        }
+        return st == HDX_E_NOMEM ? fail(st, "region table of %u regions", regions)
+                                 : fail(st, "region table upload failed");
     }
     *out = t;
     return HDX_OK;
@@ -707,16 +705,8 @@ HDX_EXPORT hdx_status hdx_region_table_create(uint32_t dims, uint32_t regions, c
 
 HDX_EXPORT hdx_status hdx_region_table_destroy(hdx_region_table t) {
     if (!t) return HDX_OK;
-    (void)hipFree(t->d_lower);
-    (void)hipFree(t->d_upper);
-    (void)hipFree(t->d_ids);
-    (void)hipFree(t->d_index);
-    for (const auto& r : t->replicas) {
-        (void)hipFree(r.lower);
-        (void)hipFree(r.upper);
-        (void)hipFree(r.ids);
-        (void)hipFree(r.index);
-    }
+    free_table_copy(t->home);
+    for (const auto& r : t->replicas) free_table_copy(r);
     delete t;
     return HDX_OK;
 }
@@ -732,22 +722,12 @@ HDX_EXPORT hdx_status hdx_lookup_region_device(hdx_region_table t, const uint64_
             return fail(HDX_E_INVALID, "subspace attribute %u >= attrs_sz %u", t->attrs[d], attrs_sz);
     hdx_status st = bind_device(-1);
     if (st != HDX_OK) return st;
-    SweepTable tb;
-    if ((st = fill_sweep_table(tb, t, t_state.device, region_ids)) != HDX_OK) return st;
     RegionArgs a{};
-    a.lower = tb.lower;
-    a.upper = tb.upper;
-    a.ids = tb.ids;
-    a.index = tb.index;
-    a.W = t->W;
-    a.index_words = t->index_words;
+    if ((st = region_view(t, t_state.device, a.t)) != HDX_OK) return st;
     a.coords = coords;
     a.out = region_ids;
     a.n = n;
     a.A = attrs_sz;
-    a.D = t->D;
-    a.R = t->R;
-    std::memcpy(a.attrs, t->attrs, sizeof a.attrs);
     HIP_TRY(launch_lookup_region(a, (hipStream_t)stream));
     return HDX_OK;
 }

@@ -284,7 +284,7 @@ HDX_EXPORT hdx_status hdx_search_regions(hdx_region_table t, const hdx_range* ra
         for (uint32_t r = 0; r < t->R; ++r) include[r] = has_replicas ? (has_replicas[r] != 0) : 1;
         return HDX_OK;
     }
-    hdx_status st = bind_device(t->device);
+    hdx_status st = bind_device(t->home.device);
     if (st != HDX_OK) return st;
     hipStream_t s;
     if ((st = thread_stream(&s)) != HDX_OK) return st;
@@ -311,7 +311,7 @@ HDX_EXPORT hdx_status hdx_search_regions(hdx_region_table t, const hdx_range* ra
             return fail(HDX_E_NOMEM, "search staging of %zu bytes", cap);
         }
         g.cap = cap;
-        g.device = t->device;
+        g.device = t->home.device;
         if (!g.tracked) {
             track_scratch(&g);
             g.tracked = true;
@@ -353,14 +353,11 @@ HDX_EXPORT hdx_status hdx_search_regions(hdx_region_table t, const hdx_range* ra
     b.A = A;
     finalize_args(b);
     HIP_TRY(launch_hash_batch(b, s));
-    a.lower = t->d_lower;
-    a.upper = t->d_upper;
+    if ((st = region_view(t, t->home.device, a.t)) != HDX_OK) return st;  // the thread is bound to the table's device
     a.hashes = b.coords;
     a.include = g.dev + o_incl;
     a.replicas = has_replicas ? g.dev + o_rep : nullptr;
     a.cleared = reinterpret_cast<uint32_t*>(g.dev + o_flag);
-    a.R = t->R;
-    a.D = t->D;
     HIP_TRY(launch_search_regions(a, s));
     HIP_TRY(hipMemcpyAsync(g.host + o_incl, g.dev + o_incl, need - o_incl, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));

@@ -103,15 +103,7 @@ hash_encoded_kernel(const EncodedArgs a) {
     const int w = threadIdx.x >> 6;
     // REGIONS: the tables' indexes and ids, one copy per workgroup, first
     uint64_t* tbl = reinterpret_cast<uint64_t*>(smem_raw);
-    if constexpr (REGIONS) {
-        for (uint32_t t = 0; t < a.T; ++t) {
-            const SweepTable& tb = a.t[t];
-            if (tb.lds_index == 0xffffffffu) continue;
-            for (uint32_t k = threadIdx.x; k < tb.index_words; k += blockDim.x) tbl[tb.lds_index + k] = tb.index[k];
-            for (uint32_t k = threadIdx.x; k < tb.R; k += blockDim.x) tbl[tb.lds_ids + k] = tb.ids[k];
-        }
-        __syncthreads();  // the kernel's only workgroup barrier (before any wave may exit)
-    }
+    if constexpr (REGIONS) stage_tables(a.t, a.T, tbl);  // the kernel's only workgroup barrier
     // wave-private LDS: G object bases {value, key}, the code table, descriptors
     uint8_t* wsmem = smem_raw + (REGIONS ? (size_t)a.lds_tables * 8 : 0) + (size_t)w * encoded_lds_per_wave(A, G, NW);
     uint64_t* bases = reinterpret_cast<uint64_t*>(wsmem);           // [G][2]
@@ -327,17 +319,7 @@ hash_encoded_kernel(const EncodedArgs a) {
             const SweepTable& tb = a.t[t];
             for (uint32_t o = lane; o < nobj; o += 64) {
                 const uint64_t* po = parked + o * A;
-                if (tb.lds_index != 0xffffffffu) {
-                    tb.out[o0 + o] = lookup_indexed_fn(tbl + tb.lds_index, tb.W, tb.D,
-                                                       [&](uint32_t d) { return po[tb.attrs[d]]; }, tbl + tb.lds_ids);
-                    continue;
-                }
-                uint64_t h[kMaxLookupDims];
-#pragma unroll
-                for (uint32_t d = 0; d < kMaxLookupDims; ++d)
-                    if (d < tb.D) h[d] = po[tb.attrs[d]];
-                tb.out[o0 + o] = tb.index ? lookup_indexed(tb.index, tb.W, tb.D, h, tb.ids)
-                                          : lookup_scan(tb.lower, tb.upper, tb.ids, tb.R, tb.D, h);
+                tb.out[o0 + o] = lookup_table<true>(tb, tbl, [&](uint32_t d) { return po[tb.attrs[d]]; });
             }
         }
     }
@@ -448,18 +430,7 @@ hipError_t launch_hash_encoded(const EncodedArgs& a_in, hipStream_t stream) {
             }
         }
         // stage each indexed table (index + ids) in LDS while they fit in 16 KiB together
-        uint32_t words = 0;
-        for (uint32_t t = 0; t < a.T; ++t) {
-            SweepTable& tb = a.t[t];
-            tb.lds_index = tb.lds_ids = 0xffffffffu;
-            const uint32_t need = tb.index_words + tb.R;
-            if (tb.index && sweep_region_lds() && (words + need) * 8 <= 16384) {
-                tb.lds_index = words;
-                tb.lds_ids = words + tb.index_words;
-                words += (need + 1) & ~1u;  // keep 16-byte alignment
-            }
-        }
-        a.lds_tables = words;
+        a.lds_tables = place_tables(a.t, a.T, sweep_region_lds());
 #if HDX_DEBUG_BUILD
         if (hash_variant() == 47) return launch_encoded<false, true, 0, 64, true>(a, stream);
 #endif

@@ -209,38 +209,47 @@ hdx_status hash_encoded_host_any(const uint8_t* codes, uint32_t A, const uint8_t
 
 }  // namespace hdx
 
-// Device copy of one subspace's region table (include/hdxhash.h).
+// One subspace's region table (include/hdxhash.h): its host arrays and a copy
+// of them on every device it has been used on.
 struct hdx_region_table_s {
-    int device;
-    uint32_t D, R;
-    uint16_t attrs[16];
-    uint64_t* d_lower;
-    uint64_t* d_upper;
-    uint64_t* d_ids;
-    uint64_t* d_index;  // interval index (NULL: lookups scan the boxes)
-    uint32_t W, index_words;
-    // host copies (the batcher's calling-thread lookups, the replicas below)
-    std::vector<uint64_t> h_lower, h_upper, h_ids, h_index;
-    // copies on the other devices a call has used the table on (the device
-    // set's entry points), made on first use and freed with the table
-    struct Replica {
+    // The arrays on one device; index NULL: the table has none (lookups scan
+    // the boxes).  lower, upper and ids carry 8 bytes of padding.
+    struct Copy {
         int device;
         uint64_t *lower, *upper, *ids, *index;
     };
+    // The copy on the device the table was created on.  home.device is the
+    // struct's first int and is compared with the calling device on every
+    // call (region_view); tests rewrite it to force the replica path.
+    Copy home;
+    uint32_t D, R, W, index_words;
+    uint16_t attrs[16];
+    // host copies (the batcher's calling-thread lookups, the replicas below);
+    // h_index empty: no index
+    std::vector<uint64_t> h_lower, h_upper, h_ids, h_index;
+    // copies on the other devices a call has used the table on (the device
+    // set's entry points), made on first use under rep_mu, freed with the table
     std::mutex rep_mu;
-    std::vector<Replica> replicas;
+    std::vector<Copy> replicas;
 };
 
 namespace hdx {
-// Table t's fields for a launch on the calling thread's current device
-// (`dev`), its id output at `out`: the table's own device arrays on the device
-// it was created on, else a replica there (uploaded on first use).
-hdx_status fill_sweep_table(SweepTable& st, hdx_region_table_s* t, int dev, uint64_t* out);
+// Table t as a launch on device `dev` (the calling thread's current device)
+// sees it: the home copy on the device the table was created on, else a
+// replica there, uploaded on first use (HDX_E_NOMEM if that fails).  The one
+// way from a handle to kernel arguments.
+hdx_status region_view(hdx_region_table_s* t, int dev, RegionView& v);
+// A fused launch's table: the view, and its id output at `out`.
+inline hdx_status fill_sweep_table(SweepTable& st, hdx_region_table_s* t, int dev, uint64_t* out) {
+    st = SweepTable{};
+    st.out = out;
+    return region_view(t, dev, st);
+}
 }  // namespace hdx
 
 // configuration::lookup_region (common/configuration.cc:698-735) on the host
-// (hdx_region_index.h): through the table's interval index when it has one,
-// else the reference's scan.
+// (hdx_region_index.h) over the table's host arrays: through its interval
+// index when it has one, else the reference's scan.
 inline uint64_t region_lookup_host(const hdx_region_table_s* t, const uint64_t* hs) {
     return hdx::region_lookup_arrays(t->D, t->R, t->W, t->attrs, t->h_lower.data(), t->h_upper.data(), t->h_ids.data(),
                                      t->h_index.empty() ? nullptr : t->h_index.data(), hs);

@@ -67,7 +67,7 @@ hipError_t launch_index_encode(const IndexArgs& a, hipStream_t stream) {
 // exactly like the reference's `!exclude` loop.
 __global__ void __launch_bounds__(256) search_regions_kernel(const SearchArgs a) {
     const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= a.R) return;
+    if (r >= a.t.R) return;
     if (a.replicas && !a.replicas[r]) {  // configuration.cc:782-785, before any range test
         a.include[r] = 0;
         return;
@@ -75,7 +75,7 @@ __global__ void __launch_bounds__(256) search_regions_kernel(const SearchArgs a)
     bool exclude = false, cleared = false;
     for (uint32_t k = 0; k < a.m && !exclude; ++k) {
         const uint32_t l = a.dim[k];
-        const uint64_t lo = a.lower[(uint64_t)r * a.D + l], hi = a.upper[(uint64_t)r * a.D + l];
+        const uint64_t lo = a.t.lower[(uint64_t)r * a.t.D + l], hi = a.t.upper[(uint64_t)r * a.t.D + l];
         if (lo > hi) {
             cleared = true;
             break;
@@ -93,8 +93,8 @@ __global__ void __launch_bounds__(256) search_regions_kernel(const SearchArgs a)
 }
 
 hipError_t launch_search_regions(const SearchArgs& a, hipStream_t stream) {
-    if (a.R == 0) return hipSuccess;
-    hipLaunchKernelGGL(search_regions_kernel, dim3((a.R + 255) / 256), dim3(256), 0, stream, a);
+    if (a.t.R == 0) return hipSuccess;
+    hipLaunchKernelGGL(search_regions_kernel, dim3((a.t.R + 255) / 256), dim3(256), 0, stream, a);
     return hipGetLastError();
 }
 

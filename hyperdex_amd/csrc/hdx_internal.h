@@ -22,16 +22,14 @@ namespace hdx {
 constexpr uint32_t kKernargCodes = 256;
 constexpr uint32_t kMaxSweepTables = 4;
 constexpr uint32_t kWavePlanSlots = 128;  // BatchArgs::plan: two 64-slot passes
-struct SweepTable {
-    const uint64_t* index;  // interval index (NULL: scan lower/upper)
-    const uint64_t* lower;
-    const uint64_t* upper;
-    const uint64_t* ids;
+// A table of a fused launch: the view (RegionView, hdx_region_index.h), where
+// its region ids go, and where the workgroup's LDS copy of an indexed table
+// lies (place_tables, hdx_region_lookup.h; only the gather forms set them).
+struct SweepTable : RegionView {
     uint64_t* out;
-    uint32_t W, D, R, index_words;
-    uint32_t lds_index, lds_ids;  // u64 offsets of the LDS copies (launch_hash_encoded)
-    uint16_t attrs[16];
+    uint32_t lds_index, lds_ids;  // u64 offsets, kNotStaged: none
 };
+static_assert(sizeof(RegionView) == 80 && sizeof(SweepTable) == 96, "kernel argument layout");
 
 struct BatchArgs {
     const uint8_t* blob;
@@ -49,7 +47,7 @@ struct BatchArgs {
     uint8_t codes[kKernargCodes];
     // fused region lookup (hash_regroup_regions_kernel): T tables, K whole
     // objects per wave, lds_tables u64 words of LDS table copies per workgroup
-    uint32_t T, K, lds_tables, win_bytes;  // win_bytes: the staged kernels' LDS window (hdx_staged.hip)
+    uint32_t T, K, lds_tables, win_bytes;  // win_bytes: unused (the retired staged kernels' LDS window)
     SweepTable t[kMaxSweepTables];
     // The wave-staged kernel's slot plan (hdx_wstage.h, PLAN; filled by its
     // launcher): every wave holds K objects of the same schema, so slot s of
@@ -58,6 +56,7 @@ struct BatchArgs {
     // code-table shuffle on the device.
     uint32_t plan[kWavePlanSlots];
 };
+static_assert(sizeof(BatchArgs) == 1248, "kernel argument layout");
 
 hipError_t launch_hash_batch(const BatchArgs& args, hipStream_t stream);
 // Wave-staged hash (hdx_wstage.hip): K whole objects per wave copied into an
@@ -98,21 +97,15 @@ int set_hash_variant(int v);  // debug build only: -2 if unknown, else the previ
 int chosen_variant(const BatchArgs& args);
 const char* variant_kernel_name(int v);
 
-// Region lookup (hdx_regions.hip): table pointers are device memory owned by
-// an hdx_region_table handle; attrs[] holds the subspace's attribute indices.
-// index (may be NULL): the table's per-dimension interval index
-// (hdx_regions.hip, region_index_build) of index_words u64, W mask words.
+// Region lookup (hdx_regions.hip) of n coordinate rows in one table: t's
+// arrays are device memory owned by an hdx_region_table handle (region_view,
+// hdx_host.h).
 struct RegionArgs {
-    const uint64_t* lower;   // [R*D]
-    const uint64_t* upper;   // [R*D]
-    const uint64_t* ids;     // [R]
-    const uint64_t* index;
-    uint32_t W, index_words;
+    RegionView t;
     const uint64_t* coords;  // [n*A]
     uint64_t* out;           // [n]
     uint64_t n;
-    uint32_t A, D, R;
-    uint16_t attrs[16];
+    uint32_t A;
 };
 
 hipError_t launch_lookup_region(const RegionArgs& a, hipStream_t stream);
@@ -148,15 +141,7 @@ struct MultiRegionArgs {
     uint64_t* out;
     uint64_t n, out_stride;
     uint32_t A, T;
-    struct Table {
-        const uint64_t* lower;
-        const uint64_t* upper;
-        const uint64_t* ids;
-        const uint64_t* index;
-        uint32_t W, index_words;
-        uint32_t D, R;
-        uint16_t attrs[16];
-    } t[kMaxMultiTables];
+    RegionView t[kMaxMultiTables];
 };
 
 hipError_t launch_lookup_regions_multi(const MultiRegionArgs& a, hipStream_t stream);
@@ -188,6 +173,7 @@ struct EncodedArgs {
     uint8_t p2[kKernargCodes];
     uint32_t S, s_magic;  // how many; ceil(2^31 / S)
 };
+static_assert(sizeof(EncodedArgs) == 1008, "kernel argument layout");
 
 hipError_t launch_hash_encoded(const EncodedArgs& a, hipStream_t stream);
 // hdx_gather.hip: n extents [src + src_off[i], +len[i]) written back to back at
@@ -297,13 +283,12 @@ hipError_t scratch_pool(hipMemPool_t* out);
 enum : uint8_t { SEARCH_NONE = 0, SEARCH_STRING_EQ = 1, SEARCH_ORDERED = 2 };
 constexpr uint32_t kMaxSearchRanges = 16;  // one range per subspace dimension
 struct SearchArgs {
-    const uint64_t* lower;   // [R*D]
-    const uint64_t* upper;   // [R*D]
+    RegionView t;            // the table: its boxes (lower, upper, R, D) are read
     const uint64_t* hashes;  // [2*m]: hash of start, hash of end
     const uint8_t* replicas; // [R] 0 = region without replicas (skipped), or NULL = all have
     uint8_t* include;        // [R]
     uint32_t* cleared;       // set when the reference would clear the server list
-    uint32_t R, D, m;
+    uint32_t m;
     uint8_t dim[kMaxSearchRanges];
     uint8_t kind[kMaxSearchRanges];
     uint8_t flags[kMaxSearchRanges];  // bit 0 has_start, bit 1 has_end

@@ -2,8 +2,9 @@
 // (common/configuration.cc:698-735): the interval index of a region table
 // (built once at hdx_region_table_create, read by the region kernels,
 // hdx_region_lookup.h) and the host lookup the batcher's calling-thread path
-// uses.  Host-only, no HIP: tests/cpp/sanitize_test.cc builds it under
-// ASan/UBSan.
+// uses, and RegionView, the one description of a table that every kernel and
+// every launch takes.  No HIP needed: tests/cpp/sanitize_test.cc builds it with
+// g++ under ASan/UBSan (HDX_HD is empty there).
 #pragma once
 
 #include <stdint.h>
@@ -12,9 +13,25 @@
 #include <cstring>
 #include <vector>
 
+#ifdef __HIPCC__
+#define HDX_HD __host__ __device__ __forceinline__
+#else
+#define HDX_HD inline
+#endif
+
 namespace hdx {
 
 constexpr uint32_t kMaxLookupDims = 16;
+// A region table as a kernel sees it: arrays on the device of the launch
+// (region_view, hdx_host.h).
+struct RegionView {
+    const uint64_t* index;  // interval index of index_words u64, W mask words (NULL: scan lower/upper)
+    const uint64_t* lower;  // [R*D]
+    const uint64_t* upper;  // [R*D]
+    const uint64_t* ids;    // [R]
+    uint32_t W, D, R, index_words;
+    uint16_t attrs[kMaxLookupDims];  // the subspace's attribute indices
+};
 // u64 words of a dimension's 257 u16 bucket starts (region_index_build),
 // stored just below its boundaries
 constexpr uint32_t kIndexBucketWords = 65;
@@ -75,33 +92,41 @@ inline void region_index_build(uint32_t D, uint32_t R, const uint64_t* lower, co
     }
 }
 
+// The W mask words of the interval that holds coordinate hv on dimension d:
+// the number of boundaries <= hv — the top byte's bucket bounds it to
+// [start[b], start[b + 1]], then a binary search over that range — picks the
+// mask.  The one copy of the search, for the host lookup below and the device
+// lookups (hdx_region_lookup.h).
+HDX_HD const uint64_t* index_interval(const uint64_t* idx, uint32_t W, uint32_t d, uint64_t hv) {
+    const uint64_t hdr = idx[d];
+    const uint64_t* B = idx + ((hdr >> 16) & 0xffffff);
+    uint16_t start[2];  // bucket starts are u16 inside u64 words: copied out, not aliased
+    __builtin_memcpy(start, reinterpret_cast<const uint16_t*>(B - kIndexBucketWords) + (hv >> 56), sizeof start);
+    uint32_t pos = start[0], cnt = start[1] - pos;
+    while (cnt) {
+        const uint32_t half = cnt >> 1;
+        if (B[pos + half] <= hv) {
+            pos += half + 1;
+            cnt -= half + 1;
+        } else {
+            cnt = half;
+        }
+    }
+    return idx + (hdr >> 40) + (size_t)pos * W;
+}
+
 // The first region (table order) whose box holds hs[attrs[d]] on every
 // dimension d (bounds inclusive), else 0 (region_id()): through the interval
-// index when the table has one (per dimension the top byte's bucket, a binary
-// search, the interval's mask; the lowest bit of the masks' AND — the device
-// form is hdx_region_lookup.h's lookup_indexed_fn), else the reference's scan.
+// index when the table has one (the lowest bit of the AND of the D intervals'
+// masks — the device form is hdx_region_lookup.h's lookup_indexed_fn), else
+// the reference's scan.
 inline uint64_t region_lookup_arrays(uint32_t D, uint32_t R, uint32_t W, const uint16_t* attrs, const uint64_t* lower,
                                      const uint64_t* upper, const uint64_t* ids, const uint64_t* idx,
                                      const uint64_t* hs) {
     if (idx) {
         uint64_t acc[kIndexMaxRegions / 64] = {~0ull, ~0ull, ~0ull, ~0ull};
         for (uint32_t d = 0; d < D; ++d) {
-            const uint64_t hdr = idx[d];
-            const uint64_t* B = idx + ((hdr >> 16) & 0xffffff);
-            const uint64_t hv = hs[attrs[d]];
-            uint16_t start[2];
-            std::memcpy(start, reinterpret_cast<const uint16_t*>(B - kIndexBucketWords) + (hv >> 56), sizeof start);
-            uint32_t pos = start[0], cnt = start[1] - pos;
-            while (cnt) {
-                const uint32_t half = cnt >> 1;
-                if (B[pos + half] <= hv) {
-                    pos += half + 1;
-                    cnt -= half + 1;
-                } else {
-                    cnt = half;
-                }
-            }
-            const uint64_t* mask = idx + (hdr >> 40) + (size_t)pos * W;
+            const uint64_t* mask = index_interval(idx, W, d, hs[attrs[d]]);
             for (uint32_t w = 0; w < W; ++w) acc[w] &= mask[w];
         }
         for (uint32_t w = 0; w < W; ++w)

@@ -13,7 +13,6 @@
 #include <stdint.h>
 
 #include <algorithm>
-#include <cstring>
 #include <mutex>
 
 #include "hdx_internal.h"
@@ -31,39 +30,29 @@ template <bool IN_LDS, bool INDEX = false>
 __global__ void __launch_bounds__(256)
 lookup_region_kernel(const RegionArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint64_t smem[];
-    const uint64_t* lower = a.lower;
-    const uint64_t* upper = a.upper;
-    const uint64_t* ids = a.ids;
-    const uint64_t* index = a.index;
-    if (INDEX) {
-        if (IN_LDS) {
-            for (uint32_t k = threadIdx.x; k < a.index_words; k += blockDim.x) smem[k] = a.index[k];
-            for (uint32_t k = threadIdx.x; k < a.R; k += blockDim.x) smem[a.index_words + k] = a.ids[k];
-            __syncthreads();
+    const RegionView& t = a.t;
+    const uint64_t* lower = t.lower;
+    const uint64_t* upper = t.upper;
+    const uint64_t* ids = t.ids;
+    const uint64_t* index = t.index;
+    if (IN_LDS) {  // an indexed table stages its index and ids, a scanned one its boxes and ids
+        if (INDEX) {
+            for (uint32_t k = threadIdx.x; k < t.index_words; k += blockDim.x) smem[k] = t.index[k];
+            for (uint32_t k = threadIdx.x; k < t.R; k += blockDim.x) smem[t.index_words + k] = t.ids[k];
             index = smem;
-            ids = smem + a.index_words;
+            ids = smem + t.index_words;
+        } else {
+            const uint32_t box = t.R * t.D;
+            for (uint32_t k = threadIdx.x; k < box; k += blockDim.x) {
+                smem[k] = t.lower[k];
+                smem[box + k] = t.upper[k];
+            }
+            for (uint32_t k = threadIdx.x; k < t.R; k += blockDim.x) smem[2 * box + k] = t.ids[k];
+            lower = smem;
+            upper = smem + box;
+            ids = smem + 2 * box;
         }
-        const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-        if (i >= a.n) return;
-        uint64_t h[kMaxLookupDims];
-        const uint64_t* row = a.coords + i * a.A;
-#pragma unroll
-        for (uint32_t d = 0; d < kMaxLookupDims; ++d)
-            if (d < a.D) h[d] = row[a.attrs[d]];
-        a.out[i] = lookup_indexed(index, a.W, a.D, h, ids);
-        return;
-    }
-    if (IN_LDS) {
-        const uint32_t box = a.R * a.D;
-        for (uint32_t k = threadIdx.x; k < box; k += blockDim.x) {
-            smem[k] = a.lower[k];
-            smem[box + k] = a.upper[k];
-        }
-        for (uint32_t k = threadIdx.x; k < a.R; k += blockDim.x) smem[2 * box + k] = a.ids[k];
         __syncthreads();
-        lower = smem;
-        upper = smem + box;
-        ids = smem + 2 * box;
     }
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.n) return;
@@ -71,34 +60,24 @@ lookup_region_kernel(const RegionArgs a) {
     const uint64_t* row = a.coords + i * a.A;
 #pragma unroll
     for (uint32_t d = 0; d < kMaxLookupDims; ++d)
-        if (d < a.D) h[d] = row[a.attrs[d]];
-    uint64_t rid = 0;  // region_id()
-    for (uint32_t r = 0; r < a.R; ++r) {
-        bool match = true;
-#pragma unroll
-        for (uint32_t d = 0; d < kMaxLookupDims; ++d)
-            if (d < a.D) match &= lower[r * a.D + d] <= h[d] && h[d] <= upper[r * a.D + d];
-        if (match) {
-            rid = ids[r];
-            break;
-        }
-    }
-    a.out[i] = rid;
+        if (d < t.D) h[d] = row[t.attrs[d]];
+    a.out[i] = INDEX ? lookup_indexed(index, t.W, t.D, h, ids) : lookup_scan(lower, upper, ids, t.R, t.D, h);
 }
 
 hipError_t launch_lookup_region(const RegionArgs& a, hipStream_t stream) {
     if (a.n == 0) return hipSuccess;
     const uint64_t blocks = (a.n + 255) / 256;
     if (blocks > 0x7fffffffULL) return hipErrorInvalidValue;
-    if (a.index) {
-        const size_t lds = ((size_t)a.index_words + a.R) * 8;
+    const RegionView& t = a.t;
+    if (t.index) {
+        const size_t lds = ((size_t)t.index_words + t.R) * 8;
         if (lds <= 48 * 1024)
             hipLaunchKernelGGL((lookup_region_kernel<true, true>), dim3((uint32_t)blocks), dim3(256), lds, stream, a);
         else
             hipLaunchKernelGGL((lookup_region_kernel<false, true>), dim3((uint32_t)blocks), dim3(256), 0, stream, a);
         return hipGetLastError();
     }
-    const size_t lds = (size_t)a.R * a.D * 16 + (size_t)a.R * 8;
+    const size_t lds = (size_t)t.R * t.D * 16 + (size_t)t.R * 8;
     if (lds <= 48 * 1024) {
         hipLaunchKernelGGL(lookup_region_kernel<true>, dim3((uint32_t)blocks), dim3(256), lds, stream, a);
     } else {
@@ -190,21 +169,7 @@ hipError_t regions_by_lookup(uint64_t n, uint32_t A, const SweepTable* t, uint32
         uint64_t* c = coords ? coords + first * A : scratch;
         if ((e = hash(first, count, c)) != hipSuccess) break;
         for (uint32_t k = 0; k < T && e == hipSuccess; ++k) {
-            RegionArgs r{};
-            r.lower = t[k].lower;
-            r.upper = t[k].upper;
-            r.ids = t[k].ids;
-            r.index = t[k].index;
-            r.W = t[k].W;
-            r.index_words = t[k].index_words;
-            r.coords = c;
-            r.out = t[k].out + first;
-            r.n = count;
-            r.A = A;
-            r.D = t[k].D;
-            r.R = t[k].R;
-            std::memcpy(r.attrs, t[k].attrs, sizeof r.attrs);
-            e = launch_lookup_region(r, stream);
+            e = launch_lookup_region(RegionArgs{t[k], c, t[k].out + first, count, A}, stream);
         }
     }
     if (scratch) {
@@ -263,7 +228,7 @@ __global__ void __launch_bounds__(256) lookup_regions_multi_kernel(const MultiRe
     const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const uint64_t t = g / a.n, i = g - t * a.n;
     if (t >= a.T) return;
-    const MultiRegionArgs::Table& tb = a.t[t];
+    const RegionView& tb = a.t[t];
     const uint64_t* lower = IN_LDS ? smem + l.lower[t] : tb.lower;
     const uint64_t* upper = IN_LDS ? smem + l.upper[t] : tb.upper;
     const uint64_t* ids = IN_LDS ? smem + l.ids[t] : tb.ids;
@@ -276,18 +241,7 @@ __global__ void __launch_bounds__(256) lookup_regions_multi_kernel(const MultiRe
         a.out[t * a.out_stride + i] = lookup_indexed(IN_LDS ? smem + l.lower[t] : tb.index, tb.W, tb.D, h, ids);
         return;
     }
-    uint64_t rid = 0;
-    for (uint32_t r = 0; r < tb.R; ++r) {
-        bool match = true;
-#pragma unroll
-        for (uint32_t d = 0; d < kMaxLookupDims; ++d)
-            if (d < tb.D) match &= lower[r * tb.D + d] <= h[d] && h[d] <= upper[r * tb.D + d];
-        if (match) {
-            rid = ids[r];
-            break;
-        }
-    }
-    a.out[t * a.out_stride + i] = rid;
+    a.out[t * a.out_stride + i] = lookup_scan(lower, upper, ids, tb.R, tb.D, h);
 }
 
 hipError_t launch_lookup_regions_multi(const MultiRegionArgs& a, hipStream_t stream) {

@@ -468,20 +468,7 @@ __device__ __forceinline__ void regroup_body(const BatchArgs& args, Lds& lds, co
         const uint32_t K = args.K, nobj = (uint32_t)(o_end - o_begin);
         auto lookup_one = [&](const SweepTable& tb, uint32_t o) {
             const uint64_t* po = res + 2ull * o * A;
-            const auto coord = [&](uint32_t d) { return po[2 * tb.attrs[d]]; };
-            uint64_t id;
-            if (tb.lds_index != 0xffffffffu) {
-                id = lookup_indexed_fn(tbl + tb.lds_index, tb.W, tb.D, coord, tbl + tb.lds_ids);
-            } else if (tb.index) {
-                id = lookup_indexed_fn(tb.index, tb.W, tb.D, coord, tb.ids);
-            } else {
-                uint64_t h[kMaxLookupDims];
-#pragma unroll
-                for (uint32_t d = 0; d < kMaxLookupDims; ++d)
-                    if (d < tb.D) h[d] = coord(d);
-                id = lookup_scan(tb.lower, tb.upper, tb.ids, tb.R, tb.D, h);
-            }
-            tb.out[o_begin + o] = id;
+            tb.out[o_begin + o] = lookup_table<true>(tb, tbl, [&](uint32_t d) { return po[2 * tb.attrs[d]]; });
         };
         if constexpr (UNI) {
             for (uint32_t t = 0; t < args.T; ++t)
@@ -539,10 +526,13 @@ __global__ void __launch_bounds__(256)
 hash_regroup_regions_kernel(const BatchArgs args) {
     __shared__ RegroupLds<C> lds;
     extern __shared__ __attribute__((aligned(16))) uint64_t tbl[];
+    // The staging is written out here, not stage_tables (hdx_region_lookup.h):
+    // through the shared function this kernel's small fused batches measured
+    // 2-3 % slower (profiles/r8/ab_region_view.jsonl's probe, 2^19 objects).
     if (args.lds_tables) {
         for (uint32_t t = 0; t < args.T; ++t) {
             const SweepTable& tb = args.t[t];
-            if (tb.lds_index == 0xffffffffu) continue;
+            if (tb.lds_index == kNotStaged) continue;
             for (uint32_t k = threadIdx.x; k < tb.index_words; k += blockDim.x) tbl[tb.lds_index + k] = tb.index[k];
             for (uint32_t k = threadIdx.x; k < tb.R; k += blockDim.x) tbl[tb.lds_ids + k] = tb.ids[k];
         }
@@ -588,18 +578,7 @@ template <int C, bool SORT, bool A4, bool ASORT, int ORDER, bool UNI = false>
 inline hipError_t launch_regroup_regions(BatchArgs args, hipStream_t stream, bool lds_ok = true) {
     // stage indexed tables in LDS while they fit in 16 KiB together and the
     // workgroup's LDS stays within 80 KiB (two workgroups per CU)
-    uint32_t words = 0;
-    const bool room = lds_ok && sizeof(RegroupLds<C>) + 16384 <= 81920;
-    for (uint32_t t = 0; t < args.T; ++t) {
-        SweepTable& tb = args.t[t];
-        tb.lds_index = tb.lds_ids = 0xffffffffu;
-        const uint32_t need = tb.index_words + tb.R;
-        if (room && tb.index && (words + need) * 8 <= 16384) {
-            tb.lds_index = words;
-            tb.lds_ids = words + tb.index_words;
-            words += (need + 1) & ~1u;
-        }
-    }
+    const uint32_t words = place_tables(args.t, args.T, lds_ok && sizeof(RegroupLds<C>) + kStagedTableBytes <= 81920);
     args.lds_tables = words;
     args.K = (C * 64) / args.A;
     if (args.K == 0) return hipErrorInvalidValue;

@@ -131,7 +131,7 @@ def test_gpu_lookup_index_vs_scan(oracle, R, scan, monkeypatch):
 @pytest.mark.gpu
 @pytest.mark.parametrize("R", [40, 256])
 def test_gpu_lookup_clustered_boundaries(oracle, R):
-    """The index's top-byte buckets (hdx_regions.hip region_index_build): box
+    """The index's top-byte buckets (hdx_region_index.h region_index_build): box
     edges crowded into two top-byte values (up to 2R boundaries in one bucket:
     a multi-step search inside it), edges exactly on bucket starts (b << 56)
     and one below, coordinates on and beside every edge."""
@@ -269,7 +269,7 @@ def test_gpu_batch_regions_by_lookup(oracle, case, with_coords):
 @pytest.mark.gpu
 def test_gpu_regions_scratch_pool_across_calls_and_shutdown(oracle):
     """The regions scratch comes from the library's per-device memory pool
-    (hdx_regions.hip region_pool): chunks reused call after call from the
+    (hdx_regions.hip scratch_pool): chunks reused call after call from the
     pool's cache, the cache trimmed by hdx_shutdown, and the next call after it
     allocating afresh — the same region ids every time (debug variant 235:
     three 64 MiB chunks per call)."""
