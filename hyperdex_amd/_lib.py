@@ -101,6 +101,12 @@ SIGNATURES = [
     ("hdx_check_encoded_device", _i32, [_vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _u32, _vp, _vp, _vp,
                                         _vp, _vp]),
     ("hdx_check_block_objects", _u32, []),
+    ("hdx_compare", _i32, [_u32, _vp, _sz, _vp, _sz, _vp]),
+    ("hdx_sorted_search", _i32, [_vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _u32, _vp, _u64, _vp, _vp,
+                                 _vp]),
+    ("hdx_sorted_search_device", _i32, [_vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _u32, _vp, _u64, _vp,
+                                        _vp, _vp, _vp, _vp]),
+    ("hdx_sort_finish_block", _u32, []),
     ("hdx_search_regions", _i32, [_vp, _vp, _u32, _vp, _vp, _vp]),
     ("hdx_search_space", _i32, [_vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp, _vp]),
     ("hdx_batcher_create", _i32, [_vp, _u32, _vp, _vp]),

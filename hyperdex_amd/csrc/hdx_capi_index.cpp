@@ -194,6 +194,26 @@ HDX_EXPORT hdx_status hdx_index_entries_fill_device(const uint32_t* types, uint3
 
 HDX_EXPORT uint32_t hdx_check_block_objects(void) { return kCheckBlock; }
 
+namespace {
+
+// The stored objects, and the STRING comparisons' constants, each at its op's
+// 8-byte-aligned offset (a.konst is zeroed), of a compiled list of checks.
+void check_objects(CheckArgs& a, const hdx_attribute_check* checks, uint32_t c, const uint8_t* keys,
+                   const uint64_t* key_off, const uint32_t* key_len, const uint8_t* vals, const uint64_t* val_off,
+                   const uint32_t* val_len) {
+    for (uint32_t k = 0; k < c; ++k)
+        if (a.op[k].op != OP_NEVER && a.op[k].op < OP_LEN_EQ && a.op[k].family == FAM_STRING && a.op[k].klen)
+            std::memcpy(reinterpret_cast<uint8_t*>(a.konst) + a.op[k].koff, checks[k].value, a.op[k].klen);
+    a.keys = keys;
+    a.key_off = key_off;
+    a.key_len = key_len;
+    a.vals = vals;
+    a.val_off = val_off;
+    a.val_len = val_len;
+}
+
+}  // namespace
+
 HDX_EXPORT hdx_status hdx_check_encoded_device(const uint32_t* types, uint32_t attrs_sz, const uint8_t* keys,
                                                const uint64_t* key_off, const uint32_t* key_len,
                                                const uint8_t* vals, const uint64_t* val_off,
@@ -208,16 +228,7 @@ HDX_EXPORT hdx_status hdx_check_encoded_device(const uint32_t* types, uint32_t a
         return fail(HDX_E_INVALID, "NULL device pointer");
     if (match && !match_count) return fail(HDX_E_INVALID, "match without match_count");
     if ((st = bind_device(-1)) != HDX_OK) return st;
-    // the STRING comparisons' constants, each at its op's 8-byte-aligned offset (a.konst is zeroed)
-    for (uint32_t k = 0; k < c; ++k)
-        if (a.op[k].op != OP_NEVER && a.op[k].op < OP_LEN_EQ && a.op[k].family == FAM_STRING && a.op[k].klen)
-            std::memcpy(reinterpret_cast<uint8_t*>(a.konst) + a.op[k].koff, checks[k].value, a.op[k].klen);
-    a.keys = keys;
-    a.key_off = key_off;
-    a.key_len = key_len;
-    a.vals = vals;
-    a.val_off = val_off;
-    a.val_len = val_len;
+    check_objects(a, checks, c, keys, key_off, key_len, vals, val_off, val_len);
     a.first_fail = first_fail;
     a.match = match;
     a.match_count = match_count;
@@ -228,6 +239,48 @@ HDX_EXPORT hdx_status hdx_check_encoded_device(const uint32_t* types, uint32_t a
     bool no_scratch = false;
     HIP_TRY(launch_check_encoded(a, (hipStream_t)stream, &no_scratch));
     if (no_scratch) return fail(HDX_E_NOMEM, "compaction scratch for %llu objects", (unsigned long long)n);
+    return HDX_OK;
+}
+
+// ---- the top-limit matches by one attribute (hdx_sorted.hip) ---------------
+
+HDX_EXPORT uint32_t hdx_sort_finish_block(void) { return kSortFinishBlock; }
+
+HDX_EXPORT hdx_status hdx_sorted_search_device(const uint32_t* types, uint32_t attrs_sz, const uint8_t* keys,
+                                               const uint64_t* key_off, const uint32_t* key_len,
+                                               const uint8_t* vals, const uint64_t* val_off,
+                                               const uint32_t* val_len, uint64_t n,
+                                               const hdx_attribute_check* checks, uint32_t c,
+                                               const hdx_sort_spec* sort, uint64_t limit, uint32_t* first_fail,
+                                               uint64_t* top, uint64_t* top_count, uint32_t* status_dev,
+                                               hdx_stream stream) {
+    SortedArgs a{};
+    hdx_status st = compile_checks(types, attrs_sz, checks, c, HDX_CHECK_BYTES_MAX, a.ck.op);
+    if (st != HDX_OK) return st;
+    int fam;
+    if ((st = sort_args(types, attrs_sz, sort, &fam)) != HDX_OK) return st;
+    if (limit > HDX_SORT_LIMIT_MAX)
+        return fail(HDX_E_INVALID, "limit=%llu above %d", (unsigned long long)limit, HDX_SORT_LIMIT_MAX);
+    if (!keys || !key_off || !key_len || !vals || !val_off || !val_len || !top || !top_count)
+        return fail(HDX_E_INVALID, "NULL device pointer");
+    if ((st = bind_device(-1)) != HDX_OK) return st;
+    check_objects(a.ck, checks, c, keys, key_off, key_len, vals, val_off, val_len);
+    a.ck.first_fail = first_fail;
+    a.ck.status = status_dev;
+    a.ck.n = n;
+    a.ck.A = attrs_sz;
+    a.ck.c = c;
+    a.top = top;
+    a.top_count = top_count;
+    a.limit = limit;
+    a.attr = sort->attr;
+    a.kind = fam < 0 ? SORT_TIE : fam == (int)FAM_STRING ? SORT_STRING : fam == (int)FAM_INT64 ? SORT_INT64 : SORT_FLOAT;
+    a.keep = sort->keep;
+    a.descending = sort->descending;
+    bool no_scratch = false;
+    HIP_TRY(launch_sorted_search(a, (hipStream_t)stream, &no_scratch));
+    if (no_scratch)
+        return fail(HDX_E_NOMEM, "sorted search scratch of %llu bytes", (unsigned long long)sorted_scratch_bytes(n));
     return HDX_OK;
 }
 

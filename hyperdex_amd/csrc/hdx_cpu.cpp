@@ -13,6 +13,11 @@
 //   hdx_hash_key     hash(const schema&, key, uint64_t* h)     common/hash.cc:48-54
 //   hdx_hash_object  hash(const schema&, key, value, hs)       common/hash.cc:56-68
 //
+// The same goes for one object's index entry, one object's attribute checks
+// and the reference's compare (hdx_index_entry, hdx_passes_checks,
+// hdx_compare), and for the sorted search over host-resident stored objects
+// (hdx_sorted_search: the daemon's own loop for what the device form leaves
+// to it; the one entry point here that allocates).
 // Every batch entry point (hdx_hash_batch_*, the sweep, the fused lookups, the
 // batcher) runs the gfx950 kernels only; nothing here is a fallback for them.
 // Pure, reentrant, lock-free, no allocation, no HIP call: works on a host with
@@ -24,6 +29,9 @@
 // Built without -ffast-math: the timestamp hash needs an IEEE division.
 #include <stdint.h>
 #include <string.h>
+
+#include <algorithm>
+#include <new>
 
 #include "hdx_cpu.h"
 #include "hdx_host_common.h"
@@ -359,5 +367,165 @@ HDX_EXPORT hdx_status hdx_passes_checks(const uint32_t* types, uint32_t attrs_sz
             break;
     }
     *first_fail = i;
+    return HDX_OK;
+}
+
+// ---- the top-limit matches by one attribute (include/hdxhash.h) ------------
+
+namespace {
+
+// datatype_{string,int64,float,timestamp}::compare(a, b) on validated operands
+// (numerics of 0 or 8 bytes): datatype_string.cc:263-285, datatype_int64.cc,
+// datatype_float.cc:256-273 (a NaN on either side gives 0).
+int compare_values(int fam, const uint8_t* a, size_t al, const uint8_t* b, size_t bl) {
+    if (fam == (int)FAM_STRING) {
+        const size_t m = al < bl ? al : bl;
+        const int c = m ? memcmp(a, b, m) : 0;
+        return c ? (c < 0 ? -1 : 1) : al < bl ? -1 : al > bl ? 1 : 0;
+    }
+    const uint64_t x = al ? cpu::le64(a) : 0, y = bl ? cpu::le64(b) : 0;  // an empty value is 0 / 0.0
+    if (fam == (int)FAM_INT64) return (int64_t)x < (int64_t)y ? -1 : (int64_t)x > (int64_t)y ? 1 : 0;
+    double p, q;
+    memcpy(&p, &x, 8);
+    memcpy(&q, &y, 8);
+    return p < q ? -1 : p > q ? 1 : 0;
+}
+
+// A sort value: the library's order is compare's, with its own rule for NaN
+// (every NaN above +inf, all NaNs tie).
+struct SortValue {
+    const uint8_t* p;
+    uint32_t len;
+    uint64_t idx;
+};
+bool is_nan(const SortValue& v) {
+    return v.len == 8 && (cpu::le64(v.p) & 0x7fffffffffffffffULL) > 0x7ff0000000000000ULL;
+}
+int sort_compare(int fam, const SortValue& a, const SortValue& b) {
+    if (fam < 0) return 0;  // attr >= attrs_sz: every object ties (search_manager.cc:361)
+    if (fam == (int)FAM_FLOAT) {
+        const bool na = is_nan(a), nb = is_nan(b);
+        if (na || nb) return na == nb ? 0 : na ? 1 : -1;
+    }
+    return compare_values(fam, a.p, a.len, b.p, b.len);
+}
+
+// a comes before b in the kept order: (value ascending, or descending with
+// largest; then index ascending)
+struct KeptOrder {
+    int fam;
+    bool largest;
+    bool operator()(const SortValue& a, const SortValue& b) const {
+        int c = sort_compare(fam, a, b);
+        if (largest) c = -c;
+        return c ? c < 0 : a.idx < b.idx;
+    }
+};
+
+// decode_value under the sweep's contract (value_walk, hdx_value_walk.h): attribute j's bytes at
+// v + pos[j - 1], len[j - 1] for the attributes named in want[0 .. w); false where the value is refused.
+bool walk_value(const uint8_t* v, uint32_t vlen, uint32_t A, const uint32_t* want, uint32_t w, uint32_t* pos,
+                uint32_t* len) {
+    if (vlen < 10) return false;
+    if ((((uint32_t)v[8] << 8) | v[9]) != ((A - 1) & 0xffffu) || A - 1 > 0xffffu) return false;
+    uint32_t at = 10;
+    for (uint32_t j = 1; j < A; ++j) {
+        if (vlen - at < 4) return false;
+        const uint32_t L = __builtin_bswap32(cpu::le32(v + at));
+        at += 4;
+        if (L > vlen - at) return false;
+        for (uint32_t k = 0; k < w; ++k)
+            if (want[k] == j) {
+                pos[k] = at;
+                len[k] = L;
+            }
+        at += L;
+    }
+    return true;
+}
+
+}  // namespace
+
+HDX_EXPORT hdx_status hdx_compare(uint32_t type, const uint8_t* a, size_t a_len, const uint8_t* b, size_t b_len,
+                                  int* cmp) {
+    const int fam = check_family(type);
+    if (fam < 0) return fail(HDX_E_BADTYPE, "hyperdatatype %u (only STRING, INT64, FLOAT, TIMESTAMP_*)", type);
+    if (!cmp || (!a && a_len) || (!b && b_len)) return fail(HDX_E_INVALID, "NULL pointer");
+    if (fam != (int)FAM_STRING && ((a_len != 0 && a_len != 8) || (b_len != 0 && b_len != 8)))
+        return fail(HDX_E_BADSIZE, "numeric values of %zu and %zu bytes", a_len, b_len);
+    *cmp = compare_values(fam, a, a_len, b, b_len);
+    return HDX_OK;
+}
+
+HDX_EXPORT hdx_status hdx_sorted_search(const uint32_t* types, uint32_t attrs_sz, const uint8_t* keys,
+                                        const uint64_t* key_off, const uint32_t* key_len, const uint8_t* vals,
+                                        const uint64_t* val_off, const uint32_t* val_len, uint64_t n,
+                                        const hdx_attribute_check* checks, uint32_t c, const hdx_sort_spec* sort,
+                                        uint64_t limit, uint64_t* top, uint64_t* top_count, uint32_t* status) {
+    CheckOp ops[HDX_MAX_CHECKS];
+    hdx_status st = compile_checks(types, attrs_sz, checks, c, UINT64_MAX, ops);
+    if (st != HDX_OK) return st;
+    int fam;
+    if ((st = sort_args(types, attrs_sz, sort, &fam)) != HDX_OK) return st;
+    if (!keys || !key_off || !key_len || !vals || !val_off || !val_len || !top || !top_count)
+        return fail(HDX_E_INVALID, "NULL pointer");
+    // the attributes the walk reports: the ops' and, last, the sort attribute
+    uint32_t want[HDX_MAX_CHECKS + 1], pos[HDX_MAX_CHECKS + 1], len[HDX_MAX_CHECKS + 1];
+    for (uint32_t k = 0; k < c; ++k) want[k] = ops[k].op != OP_NEVER ? ops[k].attr : 0;  // 0: never reported
+    want[c] = fam >= 0 ? sort->attr : 0;
+    // top[0 .. kept) is a heap with the worst of the kept on top; the values stand beside it
+    const KeptOrder order{fam, sort->keep == HDX_KEEP_LARGEST};
+    SortValue* heap = nullptr;
+    const uint64_t cap = limit < n ? limit : n;
+    if (cap) {
+        heap = new (std::nothrow) SortValue[cap];
+        if (!heap) return fail(HDX_E_NOMEM, "%llu kept values", (unsigned long long)cap);
+    }
+    uint64_t kept = 0;
+    uint32_t bits = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        const uint8_t* v = vals + val_off[i];
+        memset(pos, 0, sizeof pos);
+        memset(len, 0, sizeof len);
+        if (!walk_value(v, val_len[i], attrs_sz, want, c + 1, pos, len)) {
+            bits |= 1u << HDX_E_BADENC;
+            continue;
+        }
+        const uint8_t* key = keys + key_off[i];
+        uint32_t k = 0;
+        for (; k < c; ++k) {
+            const bool on_key = ops[k].attr == 0;
+            if (!check_passes(ops[k], checks[k].value, on_key ? key : v + pos[k], on_key ? key_len[i] : len[k])) break;
+        }
+        if (k < c) continue;
+        SortValue x{nullptr, 0, i};
+        if (fam >= 0) {
+            x.p = sort->attr == 0 ? key : v + pos[c];
+            x.len = sort->attr == 0 ? key_len[i] : len[c];
+            if (fam != (int)FAM_STRING && x.len != 0 && x.len != 8) {  // the reference's unpack asserts
+                bits |= 1u << HDX_E_BADSIZE;
+                continue;
+            }
+        }
+        if (kept < cap) {
+            heap[kept++] = x;
+            std::push_heap(heap, heap + kept, order);
+        } else if (cap && order(x, heap[0])) {
+            std::pop_heap(heap, heap + kept, order);
+            heap[kept - 1] = x;
+            std::push_heap(heap, heap + kept, order);
+        }
+    }
+    // the output: value ascending or descending, the index ascending among ties either way
+    const bool desc = sort->descending != 0;
+    std::sort(heap, heap + kept, [&](const SortValue& a, const SortValue& b) {
+        int cmp = sort_compare(fam, a, b);
+        if (desc) cmp = -cmp;
+        return cmp ? cmp < 0 : a.idx < b.idx;
+    });
+    for (uint64_t k = 0; k < kept; ++k) top[k] = heap[k].idx;
+    delete[] heap;
+    *top_count = kept;
+    if (status) *status |= bits;
     return HDX_OK;
 }

@@ -176,6 +176,21 @@ inline hdx_status compile_checks(const uint32_t* types, uint32_t attrs_sz, const
     return HDX_OK;
 }
 
+// What both forms of the sorted search (hdx_sorted_search, _device) refuse in their sort
+// argument before anything runs; *fam: the sort attribute's FAM_*, -1 where sort->attr >=
+// attrs_sz and every object ties (search_manager.cc:361).  After compile_checks: types is set.
+inline hdx_status sort_args(const uint32_t* types, uint32_t attrs_sz, const hdx_sort_spec* sort, int* fam) {
+    if (!sort) return fail(HDX_E_INVALID, "sort is NULL");
+    if (sort->keep > 1 || sort->descending > 1 || sort->reserved != 0)
+        return fail(HDX_E_INVALID, "sort: keep=%u descending=%u reserved=%u", sort->keep, sort->descending,
+                    sort->reserved);
+    *fam = -1;
+    if (sort->attr < attrs_sz && (*fam = check_family(types[sort->attr])) < 0)
+        return fail(HDX_E_BADTYPE, "sort attribute %u of hyperdatatype %u (only STRING, INT64, FLOAT, TIMESTAMP_*)",
+                    sort->attr, types[sort->attr]);
+    return HDX_OK;
+}
+
 // The relation a comparing op asks of cmp = compare(k, v), the check's value on the left (:154-173).
 // Host and device: the kernel applies the same table.
 #ifdef __HIPCC__

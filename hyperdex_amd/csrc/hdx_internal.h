@@ -273,6 +273,25 @@ struct CheckArgs {
 // check_compact_kernel.  The counts come from the library's stream-ordered
 // pool; if that allocation fails nothing is launched and *no_scratch is set.
 hipError_t launch_check_encoded(const CheckArgs& a, hipStream_t stream, bool* no_scratch);
+// The top-limit matches by one attribute (hdx_sorted.hip): the checks as
+// above (ck.first_fail may be NULL; ck.match is not used), then a 64-bit rank
+// key per matching object, a radix select of the limit-th key, the compacted
+// candidates and one workgroup's finishing sort.
+constexpr uint32_t kSortFinishBlock = 1024;  // candidates per round of the finishing step
+enum : uint32_t { SORT_TIE = 0, SORT_STRING = 1, SORT_INT64 = 2, SORT_FLOAT = 3 };
+struct SortedArgs {
+    CheckArgs ck;
+    uint64_t* top;        // [limit]
+    uint64_t* top_count;
+    uint64_t limit;       // <= HDX_SORT_LIMIT_MAX
+    uint32_t attr;        // the sort attribute, 0 = the key (unused with SORT_TIE)
+    uint32_t kind;        // SORT_*: SORT_TIE where attr >= attrs_sz, every object ties
+    uint32_t keep, descending;
+};
+// Device scratch of sorted_scratch_bytes(n) from the library's stream-ordered
+// pool; if that allocation fails nothing is launched and *no_scratch is set.
+uint64_t sorted_scratch_bytes(uint64_t n);
+hipError_t launch_sorted_search(const SortedArgs& a, hipStream_t stream, bool* no_scratch);
 // hdx_regions.hip: the library's per-device memory pool for stream-ordered
 // scratch (the regions' coordinate chunks and this scan's block sums), on the
 // calling thread's current device.

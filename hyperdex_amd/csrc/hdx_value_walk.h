@@ -3,7 +3,8 @@
 // contract — the 10-byte header, count == A - 1, every length prefix and
 // every attribute inside the value — so its verdict is the sweep's at any A.
 // Shared by the kernels that give a lane per object (index_plan_kernel,
-// hdx_index_entries.hip; check_kernel, hdx_checks.hip).  hdx_wide.hip keeps
+// hdx_index_entries.hip; check_kernel, hdx_checks.hip;
+// sorted_rank_kernel, hdx_sorted.hip).  hdx_wide.hip keeps
 // its own walk: it stores descriptors 16 at a time.
 #pragma once
 
@@ -33,6 +34,20 @@ __device__ __forceinline__ bool value_walk(const uint8_t* v, uint32_t vlen, uint
         pos += L;
     }
     return true;
+}
+
+// Attribute attr (1 .. A-1) of a value value_walk accepts: the walk up to it
+// and no further, L bytes at v + pos.
+__device__ __forceinline__ void value_attr(const uint8_t* v, uint32_t attr, uint32_t* pos_out, uint32_t* len_out) {
+    uint32_t pos = 10, L;
+    for (uint32_t j = 1;; ++j) {
+        L = __builtin_bswap32(*(walk_gu32_ptr)(v + pos));
+        pos += 4;
+        if (j == attr) break;
+        pos += L;
+    }
+    *pos_out = pos;
+    *len_out = L;
 }
 
 }  // namespace hdx

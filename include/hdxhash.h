@@ -566,6 +566,105 @@ hdx_status hdx_check_encoded_device(const uint32_t* types, uint32_t attrs_sz,
  * hdx_index_scan_block() objects (tests stand on it). */
 uint32_t hdx_check_block_objects(void);
 
+/* ---- the top-limit matches by one attribute ------------------------------- */
+
+/* What search_manager::sorted_search (daemon/search_manager.cc:305-502) does
+ * with the objects search_iterator::valid() lets through: a heap of `limit`
+ * items under datatype_info::compare of one attribute, then a sort of the
+ * survivors.  As written, the reference keeps the other end than its flag's
+ * name says (std::push_heap / pop_heap under operator< pop the greatest under
+ * <): with maximize the `limit` SMALLEST values survive and are sent in
+ * descending order, without it the `limit` largest in ascending order; the
+ * client's merge (client/pending_sorted_search.cc:187) sorts the way the name
+ * suggests.  So there is no maximize flag here but the two things it
+ * conflates, which end is kept and the direction of the output (INTEGRATION.md
+ * has both mappings).
+ *
+ * An object MATCHES when first_fail == c, exactly as in
+ * hdx_check_encoded_device — HDX_CHECK_BADENC, its status bit and "the batch
+ * reports the object and goes on" included.  A matching object whose sort
+ * attribute (the key for attr == 0) is an INT64, FLOAT or TIMESTAMP_* of
+ * neither 0 nor 8 bytes is left out, with (1u << HDX_E_BADSIZE) ORed into the
+ * status (the rule of hdx_index_entries_*: the reference's unpack asserts,
+ * datatype_int64.cc:49).  Let S be the rest, ordered by the reference's
+ * compare: STRING memcmp over the shorter length, then the lengths; INT64 and
+ * TIMESTAMP_* signed little-endian values, empty = 0; FLOAT double < and >,
+ * empty = 0.0, -0.0 ties with 0.0.
+ *   HDX_KEEP_SMALLEST  keeps the first min(limit, |S|) of S ordered by
+ *                      (value ascending, index ascending);
+ *   HDX_KEEP_LARGEST   the first min(limit, |S|) ordered by (value
+ *                      descending, index ascending).
+ * top[0 .. *top_count) holds the kept objects' indices ordered by value
+ * ascending, or descending with `descending`, and by ascending index among
+ * ties in BOTH directions; nothing is written beyond it.  The result is the
+ * same on every run.
+ *   NaN: the reference's compare returns 0 for a NaN against anything, which
+ * is no ordering (its heap's result is whatever libstdc++ happens to do).  The
+ * rule here is the library's own: every NaN, whatever its sign or payload,
+ * sorts above +inf, and all NaNs tie.
+ *   sort->attr >= attrs_sz: every object ties (search_manager.cc:361), so the
+ * result is the first `limit` matching indices.  limit == 0 is legal.
+ * Before anything runs: HDX_E_BADTYPE for a sort attribute of a type other
+ * than STRING, INT64, FLOAT or TIMESTAMP_*, and for the checks as in
+ * hdx_check_encoded_device (the same compile step); HDX_E_INVALID for a NULL
+ * pointer (first_fail and the status may be NULL), keep > 1, descending > 1,
+ * reserved != 0, and in the device form limit > HDX_SORT_LIMIT_MAX or more
+ * than HDX_CHECK_BYTES_MAX bytes of check values.  The outputs are then
+ * untouched.  Out of scope: a host-resident (_host) pipeline, the device set,
+ * larger limits on the device, packing the kept objects into a response,
+ * container or document sort attributes. */
+#define HDX_SORT_LIMIT_MAX 1024
+#define HDX_KEEP_SMALLEST 0
+#define HDX_KEEP_LARGEST  1
+typedef struct hdx_sort_spec {
+    uint32_t attr;        /* 0 = the key; >= attrs_sz: every object ties */
+    uint32_t keep;        /* HDX_KEEP_* */
+    uint32_t descending;  /* output order: 0 ascending, 1 descending */
+    uint32_t reserved;    /* 0 */
+} hdx_sort_spec;
+
+/* datatype_{string,int64,float,timestamp}::compare(a, b) on the host CPU: no
+ * device, no allocation.  *cmp = -1, 0 or 1; this is the reference's function
+ * and has no NaN rule of its own: a NaN on either side gives 0.
+ * HDX_E_BADSIZE for a numeric operand of neither 0 nor 8 bytes, HDX_E_BADTYPE
+ * for any other type, HDX_E_INVALID for a NULL pointer; *cmp is then
+ * untouched. */
+hdx_status hdx_compare(uint32_t type, const uint8_t* a, size_t a_len, const uint8_t* b, size_t b_len, int* cmp);
+
+/* The host form: stored objects in HOST memory, on the calling thread, any
+ * limit (top has room for min(limit, n) indices); it allocates min(limit, n)
+ * small records (HDX_E_NOMEM if it cannot).  *status (may be NULL) is ORed
+ * into.  The checks' values may have any size. */
+hdx_status hdx_sorted_search(const uint32_t* types, uint32_t attrs_sz,
+                             const uint8_t* keys, const uint64_t* key_off, const uint32_t* key_len,
+                             const uint8_t* vals, const uint64_t* val_off, const uint32_t* val_len,
+                             uint64_t n, const hdx_attribute_check* checks, uint32_t c,
+                             const hdx_sort_spec* sort, uint64_t limit,
+                             uint64_t* top, uint64_t* top_count, uint32_t* status);
+
+/* The device form: objects as in hdx_check_encoded_device; `types`, `checks`
+ * and `sort` are HOST memory, every other pointer is a DEVICE pointer;
+ * asynchronous on `stream`; the call reads nothing back.  first_fail (may be
+ * NULL) is hdx_check_encoded_device's; top has room for `limit` indices,
+ * top_count is one u64.  One walk per object (the checks and a 64-bit rank key
+ * in one kernel), a radix select of the limit-th key in eight histogram
+ * passes over the keys, a compaction of the candidates in index order and one
+ * workgroup's finishing sort; STRING values are told apart by their first 8
+ * bytes up to the finishing step, which compares the stored strings — a
+ * boundary prefix shared by very many strings makes that step long, never
+ * wrong.  Scratch: 17 * n + 16 * (n / 256) bytes and 17 KiB from the
+ * library's per-device stream-ordered pool; if that allocation fails the call
+ * returns HDX_E_NOMEM and launches nothing.  HDX_E_DEVICE without a device. */
+hdx_status hdx_sorted_search_device(const uint32_t* types, uint32_t attrs_sz,
+                                    const uint8_t* keys, const uint64_t* key_off, const uint32_t* key_len,
+                                    const uint8_t* vals, const uint64_t* val_off, const uint32_t* val_len,
+                                    uint64_t n, const hdx_attribute_check* checks, uint32_t c,
+                                    const hdx_sort_spec* sort, uint64_t limit,
+                                    uint32_t* first_fail, uint64_t* top, uint64_t* top_count,
+                                    uint32_t* status_dev, hdx_stream stream);
+/* Candidates the finishing step takes per round (tests stand on it). */
+uint32_t hdx_sort_finish_block(void);
+
 /* One range of a search, as range_searches() leaves it (common/range.h:40-55,
  * common/range_searches.cc:151-202): inclusive, at most one per attribute. */
 typedef struct hdx_range {
