@@ -16,7 +16,7 @@ from .hashing import (hash, hash_batch, hash_batch_host, hash_encoded, hash_enco
 from .regions import PointLeaderAbort, PointLeaders, RegionTable, lookup_region  # noqa: F401
 from .index import (IndexSpec, index_encode, index_entries, index_entries_fill, index_entries_plan,  # noqa: F401
                     index_entry, index_key_size, search_regions, search_space)
-from .checks import AttributeCheck, check_encoded, passes_checks  # noqa: F401
+from .checks import AttributeCheck, CompiledChecks, check_encoded, passes_checks, regex_match  # noqa: F401
 from .sorting import SortSpec, compare, sorted_search, sorted_search_host  # noqa: F401
 from .batcher import Batcher  # noqa: F401
 
@@ -26,4 +26,4 @@ __all__ = ["HdxError", "Attribute", "Schema", "hash", "hash_key", "hash_object",
            "init_mask", "device_set", "shutdown", "hashable", "schema_check", "RegionTable",
            "lookup_region", "PointLeaders", "PointLeaderAbort", "index_encode", "index_key_size", "IndexSpec", "index_entry",
            "index_entries", "index_entries_plan", "index_entries_fill", "search_regions", "search_space", "AttributeCheck",
-           "passes_checks", "check_encoded", "SortSpec", "compare", "sorted_search", "sorted_search_host", "Batcher", "lib"]
+           "passes_checks", "check_encoded", "CompiledChecks", "regex_match", "SortSpec", "compare", "sorted_search", "sorted_search_host", "Batcher", "lib"]

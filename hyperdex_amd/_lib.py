@@ -107,6 +107,13 @@ SIGNATURES = [
     ("hdx_sorted_search_device", _i32, [_vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _u32, _vp, _u64, _vp,
                                         _vp, _vp, _vp, _vp]),
     ("hdx_sort_finish_block", _u32, []),
+    ("hdx_regex_match", _i32, [_vp, _sz, _vp, _sz, _vp]),
+    ("hdx_checks_compile", _i32, [_vp, _u32, _vp, _u32, _vp]),
+    ("hdx_checks_free", None, [_vp]),
+    ("hdx_checks_passes", _i32, [_vp, _vp, _sz, _vp, _vp, _vp]),
+    ("hdx_checks_encoded_device", _i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp]),
+    ("hdx_checks_sorted_device", _i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp,
+                                        _vp]),
     ("hdx_search_regions", _i32, [_vp, _vp, _u32, _vp, _vp, _vp]),
     ("hdx_search_space", _i32, [_vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp, _vp]),
     ("hdx_batcher_create", _i32, [_vp, _u32, _vp, _vp]),

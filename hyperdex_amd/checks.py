@@ -73,11 +73,22 @@ def check_encoded(types, keys, key_off, key_len, vals, val_off, val_len, checks:
     (HDX_CHECK_BADENC) for a value that does not decode (status: HDX_E_BADENC's
     bit).  match: the indices with first_fail == len(checks), ascending; with
     want_match the count is read back on `stream`, which is then waited for."""
+    t = np.ascontiguousarray(np.asarray(types, dtype=np.uint32))
+    arr = _checks(checks)
+
+    def call(ptrs, n, first_fail, match, count, status_ptr, stream_ptr):
+        return lib().hdx_check_encoded_device(t.ctypes.data, len(t), *ptrs, n, arr, len(checks), first_fail, match,
+                                              count, status_ptr, stream_ptr)
+    return _check_encoded(call, keys, key_off, key_len, vals, val_off, val_len, want_match, status, stream)
+
+
+def _check_encoded(call, keys, key_off, key_len, vals, val_off, val_len, want_match, status, stream):
+    """The tensors around one of the two device forms: call(the six pointers, n, first_fail, match,
+    count, status, stream) -> hdx_status."""
     import torch
 
     from .index import _torch_stream
 
-    t = np.ascontiguousarray(np.asarray(types, dtype=np.uint32))
     n = val_off.numel()
     dev = val_off.device
     for x in (keys, key_off, key_len, vals, val_off, val_len):
@@ -91,11 +102,9 @@ def check_encoded(types, keys, key_off, key_len, vals, val_off, val_len, checks:
     # tensors without elements have no address: first_fail stands in for them; nothing reads it when n == 0
     keys, key_off, key_len, vals, val_off, val_len = [x if x.numel() else first_fail
                                                       for x in (keys, key_off, key_len, vals, val_off, val_len)]
-    check(lib().hdx_check_encoded_device(
-        t.ctypes.data, len(t), keys.data_ptr(), key_off.data_ptr(), key_len.data_ptr(), vals.data_ptr(),
-        val_off.data_ptr(), val_len.data_ptr(), n, _checks(checks), len(checks), first_fail.data_ptr(),
-        match.data_ptr() if want_match else None, count.data_ptr() if want_match else None,
-        status.data_ptr() if status is not None else None, s.cuda_stream))
+    check(call([x.data_ptr() for x in (keys, key_off, key_len, vals, val_off, val_len)], n, first_fail.data_ptr(),
+               match.data_ptr() if want_match else None, count.data_ptr() if want_match else None,
+               status.data_ptr() if status is not None else None, s.cuda_stream))
     if not want_match:
         return first_fail[:n], None
     with torch.cuda.stream(s):
@@ -103,3 +112,78 @@ def check_encoded(types, keys, key_off, key_len, vals, val_off, val_len, checks:
         host.copy_(count, non_blocking=True)
         s.synchronize()
     return first_fail[:n], match[:int(host.item())]
+
+
+HDX_REGEX_ITEMS_MAX = 63
+HDX_MAX_REGEX_CHECKS = 4
+
+
+def regex_match(regex: bytes, text: bytes) -> bool:
+    """regex_match(regex, text) of common/regex_match.cc on the host CPU
+    (hdx_regex_match): linear in len(text) whatever the pattern."""
+    out = ctypes.c_int(0)
+    check(lib().hdx_regex_match(bytes(regex), len(regex), bytes(text), len(text), ctypes.byref(out)))
+    return bool(out.value)
+
+
+class CompiledChecks:
+    """A list of checks compiled once per search (hdx_checks_compile): the one
+    form that runs REGEX on a STRING attribute.  Host memory only; usable from
+    any thread and on any device.  A context manager; freed on exit, by
+    close() or with the object."""
+
+    def __init__(self, types, checks: Sequence[AttributeCheck]):
+        self._h = None
+        t = np.ascontiguousarray(np.asarray(types, dtype=np.uint32))
+        h = ctypes.c_void_p(None)
+        check(lib().hdx_checks_compile(t.ctypes.data, len(t), _checks(checks), len(checks), ctypes.byref(h)))
+        self._h = h
+        self._free = lib().hdx_checks_free  # still there when __del__ runs at interpreter exit
+        self.attrs_sz, self.c = len(t), len(checks)
+
+    def close(self):
+        if self._h is not None:
+            self._free(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        self.close()
+
+    def _handle(self):
+        assert self._h is not None, "the compiled list was freed"
+        return self._h
+
+    def passes(self, key: bytes, values: Sequence[bytes]) -> int:
+        """As passes_checks: the index of the first failing check, len(checks) when all pass."""
+        m = len(values)
+        assert m == self.attrs_sz - 1
+        ptrs = (ctypes.c_char_p * max(m, 1))(*[bytes(v) for v in values])
+        lens = (ctypes.c_size_t * max(m, 1))(*[len(v) for v in values])
+        out = ctypes.c_uint32(0)
+        check(lib().hdx_checks_passes(self._handle(), bytes(key), len(key), ptrs, lens, ctypes.byref(out)))
+        return int(out.value)
+
+    def check_encoded(self, keys, key_off, key_len, vals, val_off, val_len, want_match=True, status=None,
+                      stream=None):
+        """As check_encoded (hdx_checks_encoded_device): returns what it returns."""
+        def call(ptrs, n, first_fail, match, count, status_ptr, stream_ptr):
+            return lib().hdx_checks_encoded_device(self._handle(), *ptrs, n, first_fail, match, count, status_ptr,
+                                                   stream_ptr)
+        return _check_encoded(call, keys, key_off, key_len, vals, val_off, val_len, want_match, status, stream)
+
+    def sorted_search(self, keys, key_off, key_len, vals, val_off, val_len, sort, limit: int, want_first_fail=True,
+                      status=None, stream=None):
+        """As sorted_search (hdx_checks_sorted_device): returns what it returns."""
+        from .sorting import _sorted_search
+
+        def call(ptrs, n, spec, lim, first_fail, top, count, status_ptr, stream_ptr):
+            return lib().hdx_checks_sorted_device(self._handle(), *ptrs, n, spec, lim, first_fail, top, count,
+                                                  status_ptr, stream_ptr)
+        return _sorted_search(call, keys, key_off, key_len, vals, val_off, val_len, sort, limit, want_first_fail,
+                              status, stream)

@@ -214,20 +214,19 @@ void check_objects(CheckArgs& a, const hdx_attribute_check* checks, uint32_t c, 
 
 }  // namespace
 
-HDX_EXPORT hdx_status hdx_check_encoded_device(const uint32_t* types, uint32_t attrs_sz, const uint8_t* keys,
-                                               const uint64_t* key_off, const uint32_t* key_len,
-                                               const uint8_t* vals, const uint64_t* val_off,
-                                               const uint32_t* val_len, uint64_t n,
-                                               const hdx_attribute_check* checks, uint32_t c,
-                                               uint32_t* first_fail, uint64_t* match, uint64_t* match_count,
-                                               uint32_t* status_dev, hdx_stream stream) {
-    CheckArgs a{};
-    hdx_status st = compile_checks(types, attrs_sz, checks, c, HDX_CHECK_BYTES_MAX, a.op);
-    if (st != HDX_OK) return st;
+namespace {
+
+// Both forms behind their compile step: a.op holds the ops; rx: NULL or the compiled list's programs.
+hdx_status check_encoded_run(CheckArgs& a, const RegexArgs* rx, uint32_t attrs_sz, const hdx_attribute_check* checks,
+                             uint32_t c, const uint8_t* keys, const uint64_t* key_off, const uint32_t* key_len,
+                             const uint8_t* vals, const uint64_t* val_off, const uint32_t* val_len, uint64_t n,
+                             uint32_t* first_fail, uint64_t* match, uint64_t* match_count, uint32_t* status_dev,
+                             hdx_stream stream) {
     if (!keys || !key_off || !key_len || !vals || !val_off || !val_len || !first_fail)
         return fail(HDX_E_INVALID, "NULL device pointer");
     if (match && !match_count) return fail(HDX_E_INVALID, "match without match_count");
-    if ((st = bind_device(-1)) != HDX_OK) return st;
+    hdx_status st = bind_device(-1);
+    if (st != HDX_OK) return st;
     check_objects(a, checks, c, keys, key_off, key_len, vals, val_off, val_len);
     a.first_fail = first_fail;
     a.match = match;
@@ -237,28 +236,64 @@ HDX_EXPORT hdx_status hdx_check_encoded_device(const uint32_t* types, uint32_t a
     a.A = attrs_sz;
     a.c = c;
     bool no_scratch = false;
-    HIP_TRY(launch_check_encoded(a, (hipStream_t)stream, &no_scratch));
+    HIP_TRY(launch_check_encoded(a, (hipStream_t)stream, &no_scratch, rx));
     if (no_scratch) return fail(HDX_E_NOMEM, "compaction scratch for %llu objects", (unsigned long long)n);
     return HDX_OK;
+}
+
+// The ops and programs of a compiled list as kernel arguments.
+void compiled_args(const hdx_checks_s* h, CheckOp* ops, RegexArgs& rx) {
+    std::memcpy(ops, h->ops, sizeof h->ops);
+    rx = RegexArgs{};
+    rx.count = h->nrx;
+    std::memcpy(rx.prog, h->progs, sizeof h->progs);
+}
+
+}  // namespace
+
+HDX_EXPORT hdx_status hdx_check_encoded_device(const uint32_t* types, uint32_t attrs_sz, const uint8_t* keys,
+                                               const uint64_t* key_off, const uint32_t* key_len,
+                                               const uint8_t* vals, const uint64_t* val_off,
+                                               const uint32_t* val_len, uint64_t n,
+                                               const hdx_attribute_check* checks, uint32_t c,
+                                               uint32_t* first_fail, uint64_t* match, uint64_t* match_count,
+                                               uint32_t* status_dev, hdx_stream stream) {
+    CheckArgs a{};
+    const hdx_status st = compile_checks(types, attrs_sz, checks, c, HDX_CHECK_BYTES_MAX, a.op);
+    if (st != HDX_OK) return st;
+    return check_encoded_run(a, nullptr, attrs_sz, checks, c, keys, key_off, key_len, vals, val_off, val_len, n,
+                             first_fail, match, match_count, status_dev, stream);
+}
+
+HDX_EXPORT hdx_status hdx_checks_encoded_device(hdx_checks h, const uint8_t* keys, const uint64_t* key_off,
+                                                const uint32_t* key_len, const uint8_t* vals,
+                                                const uint64_t* val_off, const uint32_t* val_len, uint64_t n,
+                                                uint32_t* first_fail, uint64_t* match, uint64_t* match_count,
+                                                uint32_t* status_dev, hdx_stream stream) {
+    if (!h) return fail(HDX_E_INVALID, "the compiled list is NULL");
+    CheckArgs a{};
+    RegexArgs rx;
+    compiled_args(h, a.op, rx);
+    return check_encoded_run(a, &rx, h->attrs_sz, h->checks, h->c, keys, key_off, key_len, vals, val_off, val_len, n,
+                             first_fail, match, match_count, status_dev, stream);
 }
 
 // ---- the top-limit matches by one attribute (hdx_sorted.hip) ---------------
 
 HDX_EXPORT uint32_t hdx_sort_finish_block(void) { return kSortFinishBlock; }
 
-HDX_EXPORT hdx_status hdx_sorted_search_device(const uint32_t* types, uint32_t attrs_sz, const uint8_t* keys,
-                                               const uint64_t* key_off, const uint32_t* key_len,
-                                               const uint8_t* vals, const uint64_t* val_off,
-                                               const uint32_t* val_len, uint64_t n,
-                                               const hdx_attribute_check* checks, uint32_t c,
-                                               const hdx_sort_spec* sort, uint64_t limit, uint32_t* first_fail,
-                                               uint64_t* top, uint64_t* top_count, uint32_t* status_dev,
-                                               hdx_stream stream) {
-    SortedArgs a{};
-    hdx_status st = compile_checks(types, attrs_sz, checks, c, HDX_CHECK_BYTES_MAX, a.ck.op);
-    if (st != HDX_OK) return st;
+namespace {
+
+// Both forms behind their compile step, as check_encoded_run.
+hdx_status sorted_search_run(SortedArgs& a, const RegexArgs* rx, const uint32_t* types, uint32_t attrs_sz,
+                             const hdx_attribute_check* checks, uint32_t c, const uint8_t* keys,
+                             const uint64_t* key_off, const uint32_t* key_len, const uint8_t* vals,
+                             const uint64_t* val_off, const uint32_t* val_len, uint64_t n, const hdx_sort_spec* sort,
+                             uint64_t limit, uint32_t* first_fail, uint64_t* top, uint64_t* top_count,
+                             uint32_t* status_dev, hdx_stream stream) {
     int fam;
-    if ((st = sort_args(types, attrs_sz, sort, &fam)) != HDX_OK) return st;
+    hdx_status st = sort_args(types, attrs_sz, sort, &fam);
+    if (st != HDX_OK) return st;
     if (limit > HDX_SORT_LIMIT_MAX)
         return fail(HDX_E_INVALID, "limit=%llu above %d", (unsigned long long)limit, HDX_SORT_LIMIT_MAX);
     if (!keys || !key_off || !key_len || !vals || !val_off || !val_len || !top || !top_count)
@@ -278,10 +313,40 @@ HDX_EXPORT hdx_status hdx_sorted_search_device(const uint32_t* types, uint32_t a
     a.keep = sort->keep;
     a.descending = sort->descending;
     bool no_scratch = false;
-    HIP_TRY(launch_sorted_search(a, (hipStream_t)stream, &no_scratch));
+    HIP_TRY(launch_sorted_search(a, (hipStream_t)stream, &no_scratch, rx));
     if (no_scratch)
         return fail(HDX_E_NOMEM, "sorted search scratch of %llu bytes", (unsigned long long)sorted_scratch_bytes(n));
     return HDX_OK;
+}
+
+}  // namespace
+
+HDX_EXPORT hdx_status hdx_sorted_search_device(const uint32_t* types, uint32_t attrs_sz, const uint8_t* keys,
+                                               const uint64_t* key_off, const uint32_t* key_len,
+                                               const uint8_t* vals, const uint64_t* val_off,
+                                               const uint32_t* val_len, uint64_t n,
+                                               const hdx_attribute_check* checks, uint32_t c,
+                                               const hdx_sort_spec* sort, uint64_t limit, uint32_t* first_fail,
+                                               uint64_t* top, uint64_t* top_count, uint32_t* status_dev,
+                                               hdx_stream stream) {
+    SortedArgs a{};
+    const hdx_status st = compile_checks(types, attrs_sz, checks, c, HDX_CHECK_BYTES_MAX, a.ck.op);
+    if (st != HDX_OK) return st;
+    return sorted_search_run(a, nullptr, types, attrs_sz, checks, c, keys, key_off, key_len, vals, val_off, val_len, n,
+                             sort, limit, first_fail, top, top_count, status_dev, stream);
+}
+
+HDX_EXPORT hdx_status hdx_checks_sorted_device(hdx_checks h, const uint8_t* keys, const uint64_t* key_off,
+                                               const uint32_t* key_len, const uint8_t* vals, const uint64_t* val_off,
+                                               const uint32_t* val_len, uint64_t n, const hdx_sort_spec* sort,
+                                               uint64_t limit, uint32_t* first_fail, uint64_t* top,
+                                               uint64_t* top_count, uint32_t* status_dev, hdx_stream stream) {
+    if (!h) return fail(HDX_E_INVALID, "the compiled list is NULL");
+    SortedArgs a{};
+    RegexArgs rx;
+    compiled_args(h, a.ck.op, rx);
+    return sorted_search_run(a, &rx, h->types, h->attrs_sz, h->checks, h->c, keys, key_off, key_len, vals, val_off,
+                             val_len, n, sort, limit, first_fail, top, top_count, status_dev, stream);
 }
 
 HDX_EXPORT hdx_status hdx_search_regions(hdx_region_table t, const hdx_range* ranges, uint32_t nranges,

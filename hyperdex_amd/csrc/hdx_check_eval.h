@@ -110,6 +110,20 @@ constexpr size_t check_lds_bytes(uint32_t B, uint32_t c) { return kCheckConstByt
 
 // Every thread of the workgroup: stage the constants the ops use and clear
 // this lane's descriptors; ends with a barrier.
+// As compiled for gfx950 this stages far more than konst_words, and only the
+// LDS behind this function's barrier may be relied on.  The loop over the ops
+// became a pointer at op[k].op (kernel arguments + 0x62 + 24 k) and
+// `s_load_dwordx2 ..., 0x2` for klen and koff; a gfx950 scalar load drops the
+// low two bits of its base and of its offset separately (measured: base + 0x62
+// with offset 2 returns the dwords at + 0x60 and + 0x64), so the loop reads
+// {attr | op << 16 | family << 24, klen}.  For any STRING comparison the count
+// comes out at 8192 words or more: the staging loop reads that far behind the
+// kernel arguments and writes over all of the workgroup's LDS (the hardware
+// drops what lies past the allocation).  The results do not depend on it: the
+// constants' own words are right, and off / len are cleared afterwards.
+// Reading the ops as aligned dwords removes it, but measured 0.24-0.5 ms
+// slower per 10 M objects than this form for a reason not found, so it is left
+// to a change of its own.
 template <uint32_t B>
 __device__ __forceinline__ void check_lds_init(const CheckArgs& a, const CheckLds& s) {
     const uint32_t c = a.c, tid = threadIdx.x;
@@ -125,13 +139,61 @@ __device__ __forceinline__ void check_lds_init(const CheckArgs& a, const CheckLd
     __syncthreads();
 }
 
+// ---- OP_REGEX: a compiled list's regex_match ops (hdx_regex.h) --------------
+//
+// A lane keeps one 64-bit state word; per text byte one read of the op's
+// byte-class table (256 x 8 B in LDS, built by the workgroup from the kernel
+// arguments: no device allocation, no upload) and regex_step.  The text comes
+// by the loads above.  The trip count is the text's length at most: a lane
+// leaves at accept, or once every position has died (anchored patterns).
+// The table reads are random 8-byte LDS reads per lane (ds_read_b64: two
+// groups of 32 lanes, bank (address / 4) mod 64): lanes of a group reading
+// the same byte share one read, different bytes congruent mod 32 take turns.
+struct RegexLds {
+    const RegexArgs* rx;
+    const uint64_t* table;  // [rx->count][256]
+};
+constexpr size_t regex_lds_bytes(uint32_t count) { return (size_t)count * 256 * 8; }
+
+// Every thread of the workgroup, behind check_lds_init's barrier (as compiled,
+// its staging loop writes past the carve: see there): the tables at `at`
+// (8-byte aligned: the carve is whole u64s); returns the first byte behind
+// them.  Ends with a barrier.
+template <uint32_t B>
+__device__ __forceinline__ uint32_t* regex_lds_init(RegexLds& rl, const RegexArgs& rx, uint32_t* at) {
+    uint64_t* table = reinterpret_cast<uint64_t*>(at);
+    for (uint32_t r = 0; r < rx.count; ++r)
+        for (uint32_t b = threadIdx.x; b < 256; b += B) table[r * 256 + b] = regex_class(rx.prog[r], b);
+    rl.rx = &rx;
+    rl.table = table;
+    __syncthreads();
+    return reinterpret_cast<uint32_t*>(table + rx.count * 256);
+}
+
+__device__ __forceinline__ bool regex_run(const RegexProg& g, const uint64_t* table, const uint8_t* p, uint32_t len) {
+    uint64_t s = regex_start(g);
+    if (regex_accepted(g, s)) return true;
+    for (uint32_t w = 0; w < len; w += 8) {
+        const uint32_t r = std::min(len - w, 8u);
+        uint64_t word = word_bytes(p + w, r);
+        for (uint32_t b = 0; b < r; ++b, word >>= 8) {
+            s = regex_step(g, s, table[word & 0xff]);
+            if (regex_accepted(g, s)) return true;
+            if (!s) return false;
+        }
+    }
+    return regex_at_end(g, s);
+}
+
 // Object i (< a.n): the walk (value_walk, the full walk: the verdict is the
 // sweep's at any A), {offset, length} of the attributes the ops name kept in
 // LDS, then the ops in order up to the first false one.  Returns first_fail:
 // HDX_CHECK_BADENC where the value does not decode.  also(j, pos, L) sees
-// every attribute of the walk as well.
-template <uint32_t B, typename F>
-__device__ __forceinline__ uint32_t check_object(const CheckArgs& a, const CheckLds& s, uint64_t i, F&& also) {
+// every attribute of the walk as well.  RX: the list may hold OP_REGEX ops
+// (rx is theirs); the one-shot entry points' kernels are built without.
+template <uint32_t B, bool RX, typename F>
+__device__ __forceinline__ uint32_t check_object(const CheckArgs& a, const CheckLds& s, const RegexLds& rx, uint64_t i,
+                                                 F&& also) {
     const uint32_t c = a.c, tid = threadIdx.x;
     const uint8_t* v = a.vals + a.val_off[i];
     const bool ok = value_walk(v, a.val_len[i], a.A, [&](uint32_t j, uint32_t pos, uint32_t L) {
@@ -150,6 +212,14 @@ __device__ __forceinline__ uint32_t check_object(const CheckArgs& a, const Check
         bool t = false;
         if (o.op != OP_NEVER) {
             const bool on_key = o.attr == 0;
+            if constexpr (RX) {
+                if (o.op == OP_REGEX) {
+                    if (!regex_run(rx.rx->prog[o.koff], rx.table + o.koff * 256, on_key ? key : v + s.off[k * B + tid],
+                                   on_key ? kl : s.len[k * B + tid]))
+                        return k;
+                    continue;
+                }
+            }
             t = eval_op(o, s.konst, on_key ? key : v + s.off[k * B + tid], on_key ? kl : s.len[k * B + tid]);
         }
         if (!t) return k;

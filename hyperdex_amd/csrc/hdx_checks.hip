@@ -33,19 +33,25 @@ namespace hdx {
 
 namespace {
 
-// Dynamic LDS: the checks' (check_lds_carve, hdx_check_eval.h), then the
-// waves' pass counts.
-__global__ void __launch_bounds__(kCheckBlock) check_kernel(const CheckArgs a, uint64_t* block_pass) {
+// Dynamic LDS: the checks' (check_lds_carve, hdx_check_eval.h), for a list
+// with OP_REGEX ops their byte-class tables (regex_lds_bytes), then the waves'
+// pass counts.  RXA: nothing — the one-shot entry points' kernel, and a
+// compiled list's without OP_REGEX ops — or RegexArgs, a third kernel argument.
+template <typename... RXA>
+__global__ void __launch_bounds__(kCheckBlock) check_kernel(const CheckArgs a, uint64_t* block_pass, const RXA... rx) {
     extern __shared__ __attribute__((aligned(16))) uint64_t check_lds[];
     constexpr uint32_t B = kCheckBlock;
+    constexpr bool RX = sizeof...(RXA) != 0;
     const uint32_t c = a.c, tid = threadIdx.x;
     uint32_t* s_cnt;
     const CheckLds s = check_lds_carve<B>(check_lds, c, &s_cnt);
+    RegexLds rl{};
     check_lds_init<B>(a, s);
+    if constexpr (RX) s_cnt = regex_lds_init<B>(rl, rx..., s_cnt);
     const uint64_t i = (uint64_t)blockIdx.x * B + tid;
     bool badenc = false, pass = false;
     if (i < a.n) {
-        const uint32_t ff = check_object<B>(a, s, i, [](uint32_t, uint32_t, uint32_t) {});
+        const uint32_t ff = check_object<B, RX>(a, s, rl, i, [](uint32_t, uint32_t, uint32_t) {});
         badenc = ff == HDX_CHECK_BADENC;
         pass = ff == c;
         a.first_fail[i] = ff;
@@ -87,7 +93,10 @@ __global__ void __launch_bounds__(kCheckBlock) check_compact_kernel(const CheckA
 
 }  // namespace
 
-hipError_t launch_check_encoded(const CheckArgs& a, hipStream_t stream, bool* no_scratch) {
+hipError_t launch_check_encoded(const CheckArgs& a, hipStream_t stream, bool* no_scratch, const RegexArgs* rx) {
+    static_assert(check_lds_bytes(kCheckBlock, HDX_MAX_CHECKS) + regex_lds_bytes(HDX_MAX_REGEX_CHECKS) +
+                          (kCheckBlock / 64) * 4 < (64 << 10),
+                  "dynamic LDS at c = 16 with every regex op");
     *no_scratch = false;
     const uint64_t blocks = (a.n + kCheckBlock - 1) / kCheckBlock;
     if (blocks > 0x7fffffffULL) return hipErrorInvalidValue;
@@ -105,7 +114,11 @@ hipError_t launch_check_encoded(const CheckArgs& a, hipStream_t stream, bool* no
         }
     }
     const size_t lds = check_lds_bytes(kCheckBlock, a.c) + (kCheckBlock / 64) * 4;
-    hipLaunchKernelGGL(check_kernel, dim3((uint32_t)blocks), dim3(kCheckBlock), lds, stream, a, counts);
+    if (rx && rx->count)
+        hipLaunchKernelGGL(check_kernel<RegexArgs>, dim3((uint32_t)blocks), dim3(kCheckBlock),
+                           lds + regex_lds_bytes(rx->count), stream, a, counts, *rx);
+    else
+        hipLaunchKernelGGL(check_kernel<>, dim3((uint32_t)blocks), dim3(kCheckBlock), lds, stream, a, counts);
     hipError_t e = hipGetLastError();
     if (counts) {
         if (e == hipSuccess) e = scan_exclusive(counts, blocks, counts + blocks, stream);

@@ -318,7 +318,7 @@ namespace {
 // compile_checks decided: validate(v), then the comparison.  k: the check's
 // own bytes (a STRING comparison reads them in place).
 bool check_passes(const CheckOp& o, const uint8_t* k, const uint8_t* v, size_t len) {
-    if (o.op == OP_NEVER) return false;
+    if (o.op == OP_NEVER || o.op > OP_LEN_GE) return false;  // OP_REGEX has its own path (object_first_fail)
     if (o.op >= OP_LEN_EQ) {  // :178-199, T == STRING: length(v) = its size
         const int64_t L = (int64_t)len, tmp = (int64_t)o.imm;
         return o.op == OP_LEN_EQ ? L == tmp : o.op == OP_LEN_LE ? L <= tmp : L >= tmp;
@@ -344,15 +344,14 @@ bool check_passes(const CheckOp& o, const uint8_t* k, const uint8_t* v, size_t l
     return check_relation(o.op, cmp);
 }
 
-}  // namespace
-
-// passes_attribute_checks, common/attribute_check.cc:209-237
-HDX_EXPORT hdx_status hdx_passes_checks(const uint32_t* types, uint32_t attrs_sz, const uint8_t* key,
-                                        size_t key_len, const uint8_t* const* values, const size_t* value_lens,
-                                        const hdx_attribute_check* checks, uint32_t c, uint32_t* first_fail) {
-    CheckOp ops[HDX_MAX_CHECKS];
-    const hdx_status st = compile_checks(types, attrs_sz, checks, c, UINT64_MAX, ops);
-    if (st != HDX_OK) return st;
+// passes_attribute_checks (common/attribute_check.cc:209-237) over compiled ops, for both per-object
+// forms: the pointer checks, then the ops in order up to the first false one.  progs / table: the
+// compiled form's regex programs and byte classes (op k's at ops[k].koff), NULL for the one-shot form,
+// whose compile step makes no OP_REGEX.
+hdx_status object_first_fail(const CheckOp* ops, const hdx_attribute_check* checks, uint32_t c, uint32_t attrs_sz,
+                             const RegexProg* progs, const uint64_t (*table)[256], const uint8_t* key,
+                             size_t key_len, const uint8_t* const* values, const size_t* value_lens,
+                             uint32_t* first_fail) {
     if (!first_fail || (!key && key_len) || (attrs_sz > 1 && (!values || !value_lens)))
         return fail(HDX_E_INVALID, "NULL pointer");
     for (uint32_t i = 0; i < c; ++i)
@@ -362,12 +361,84 @@ HDX_EXPORT hdx_status hdx_passes_checks(const uint32_t* types, uint32_t attrs_sz
     for (; i < c; ++i) {
         const CheckOp& o = ops[i];
         const bool on_key = o.attr == 0;
-        if (!check_passes(o, checks[i].value, on_key ? key : values[o.attr - 1],
-                          on_key ? key_len : value_lens[o.attr - 1]))
+        const uint8_t* v = on_key ? key : values[o.attr - 1];
+        const size_t len = on_key ? key_len : value_lens[o.attr - 1];
+        if (!(o.op == OP_REGEX && progs ? regex_run_host(progs[o.koff], table[o.koff], v, len)
+                                        : check_passes(o, checks[i].value, v, len)))
             break;
     }
     *first_fail = i;
     return HDX_OK;
+}
+
+}  // namespace
+
+// passes_attribute_checks, common/attribute_check.cc:209-237
+HDX_EXPORT hdx_status hdx_passes_checks(const uint32_t* types, uint32_t attrs_sz, const uint8_t* key,
+                                        size_t key_len, const uint8_t* const* values, const size_t* value_lens,
+                                        const hdx_attribute_check* checks, uint32_t c, uint32_t* first_fail) {
+    CheckOp ops[HDX_MAX_CHECKS];
+    const hdx_status st = compile_checks(types, attrs_sz, checks, c, UINT64_MAX, ops);
+    if (st != HDX_OK) return st;
+    return object_first_fail(ops, checks, c, attrs_sz, nullptr, nullptr, key, key_len, values, value_lens, first_fail);
+}
+
+// ---- a list of checks compiled once per search (include/hdxhash.h) ---------
+
+HDX_EXPORT hdx_status hdx_regex_match(const uint8_t* regex, size_t regex_len, const uint8_t* text, size_t text_len,
+                                      int* matched) {
+    if (!matched || (!regex && regex_len) || (!text && text_len)) return fail(HDX_E_INVALID, "NULL pointer");
+    RegexProg g;
+    if (!regex_parse(regex, regex_len, &g))
+        return fail(HDX_E_INVALID, "a pattern of more than %d items", HDX_REGEX_ITEMS_MAX);
+    *matched = regex_run_host(g, nullptr, text, text_len) ? 1 : 0;
+    return HDX_OK;
+}
+
+HDX_EXPORT hdx_status hdx_checks_compile(const uint32_t* types, uint32_t attrs_sz, const hdx_attribute_check* checks,
+                                         uint32_t c, hdx_checks* out) {
+    CheckOp ops[HDX_MAX_CHECKS];
+    RegexProg progs[HDX_MAX_REGEX_CHECKS];
+    uint32_t nrx = 0;
+    const hdx_status st = compile_checks(types, attrs_sz, checks, c, HDX_CHECK_BYTES_MAX, ops, progs, &nrx);
+    if (st != HDX_OK) return st;
+    if (!out) return fail(HDX_E_INVALID, "out is NULL");
+    size_t bytes = 0;
+    for (uint32_t i = 0; i < c; ++i) bytes += checks[i].value_len;
+    const size_t types_at = sizeof(hdx_checks_s), bytes_at = types_at + (size_t)attrs_sz * 4;
+    void* block = ::operator new(bytes_at + bytes, std::nothrow);
+    if (!block) return fail(HDX_E_NOMEM, "a compiled list of %zu bytes", bytes_at + bytes);
+    hdx_checks_s* h = new (block) hdx_checks_s{};
+    uint8_t* base = static_cast<uint8_t*>(block);
+    memcpy(base + types_at, types, (size_t)attrs_sz * 4);
+    h->types = reinterpret_cast<const uint32_t*>(base + types_at);
+    h->attrs_sz = attrs_sz;
+    h->c = c;
+    h->nrx = nrx;
+    uint8_t* at = base + bytes_at;
+    for (uint32_t i = 0; i < c; ++i) {
+        h->checks[i] = checks[i];
+        h->ops[i] = ops[i];
+        if (checks[i].value_len) memcpy(at, checks[i].value, checks[i].value_len);
+        h->checks[i].value = at;
+        at += checks[i].value_len;
+    }
+    for (uint32_t r = 0; r < nrx; ++r) {
+        h->progs[r] = progs[r];
+        for (uint32_t b = 0; b < 256; ++b) h->table[r][b] = regex_class(progs[r], b);
+    }
+    *out = h;
+    return HDX_OK;
+}
+
+HDX_EXPORT void hdx_checks_free(hdx_checks h) { ::operator delete(h); }
+
+HDX_EXPORT hdx_status hdx_checks_passes(hdx_checks h, const uint8_t* key, size_t key_len,
+                                        const uint8_t* const* values, const size_t* value_lens,
+                                        uint32_t* first_fail) {
+    if (!h) return fail(HDX_E_INVALID, "the compiled list is NULL");
+    return object_first_fail(h->ops, h->checks, h->c, h->attrs_sz, h->progs, h->table, key, key_len, values,
+                             value_lens, first_fail);
 }
 
 // ---- the top-limit matches by one attribute (include/hdxhash.h) ------------

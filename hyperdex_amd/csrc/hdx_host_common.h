@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "../../include/hdxhash.h"
+#include "hdx_regex.h"
 
 #define HDX_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -76,13 +77,15 @@ hdx_status fail(hdx_status s, const char* fmt, ...) __attribute__((format(printf
 // Everything of passes_attribute_check that does not depend on the object is
 // decided by compile_checks; what is left per object is the attribute's own
 // validate() (:141) and one comparison.
-enum : uint8_t { OP_NEVER = 0, OP_EQ, OP_LT, OP_LE, OP_GE, OP_GT, OP_LEN_EQ, OP_LEN_LE, OP_LEN_GE };
+// OP_REGEX (regex_match(k, v), :174-177) comes only out of the compiled form (hdx_checks_compile).
+enum : uint8_t { OP_NEVER = 0, OP_EQ, OP_LT, OP_LE, OP_GE, OP_GT, OP_LEN_EQ, OP_LEN_LE, OP_LEN_GE, OP_REGEX };
 enum : uint8_t { FAM_STRING = 0, FAM_INT64 = 1, FAM_FLOAT = 2 };
 struct CheckOp {
     uint16_t attr;   // 0: the key; 0 also with OP_NEVER, which reads nothing
     uint8_t op, family;
     uint32_t klen;   // FAM_STRING comparisons: the constant's length
-    uint32_t koff;   // ... and its 8-byte-aligned offset in the packed constants (pack_check_constants)
+    uint32_t koff;   // ... and its 8-byte-aligned offset in the packed constants (pack_check_constants);
+                     // OP_REGEX: the index of its program
     uint32_t pad_;
     uint64_t imm;    // numeric comparisons: k's little-endian bits (empty: 0); OP_LEN_*: tmp
 };
@@ -103,9 +106,12 @@ inline int check_family(uint32_t type) {
 // The argument checks of both forms, then ops[0..c).  max_bytes: the cap on
 // the sum of the checks' value_len (the device form's HDX_CHECK_BYTES_MAX: its
 // constants travel in the kernel arguments; the CPU form reads them in place
-// and has none).
+// and has none).  progs: NULL for the one-shot entry points, which refuse REGEX
+// on a STRING attribute; the compiled form's HDX_MAX_REGEX_CHECKS programs,
+// *nprogs of them used, op k's at ops[k].koff.
 inline hdx_status compile_checks(const uint32_t* types, uint32_t attrs_sz, const hdx_attribute_check* checks,
-                                 uint32_t c, uint64_t max_bytes, CheckOp* ops) {
+                                 uint32_t c, uint64_t max_bytes, CheckOp* ops, RegexProg* progs = nullptr,
+                                 uint32_t* nprogs = nullptr) {
     if (!types) return fail(HDX_E_INVALID, "types is NULL");
     if (attrs_sz == 0 || attrs_sz > HDX_MAX_ATTRS)
         return fail(HDX_E_INVALID, "attrs_sz=%u outside [1, %d]", attrs_sz, HDX_MAX_ATTRS);
@@ -119,6 +125,7 @@ inline hdx_status compile_checks(const uint32_t* types, uint32_t attrs_sz, const
         bytes += checks[i].value_len;
     }
     uint32_t koff = 0;
+    if (nprogs) *nprogs = 0;
     for (uint32_t i = 0; i < c; ++i) {
         const hdx_attribute_check& ck = checks[i];
         CheckOp& o = ops[i];
@@ -129,8 +136,20 @@ inline hdx_status compile_checks(const uint32_t* types, uint32_t attrs_sz, const
         if (fam < 0)
             return fail(HDX_E_BADTYPE, "check %u: attribute %u of hyperdatatype %u (only STRING, INT64, FLOAT, TIMESTAMP_*)",
                         i, ck.attr, T);
-        if (ck.predicate == 9733 && T == 9217 && D == 9217)  // :174-177, the one case that runs regex_match
-            return fail(HDX_E_BADTYPE, "check %u: REGEX on a STRING attribute is not supported", i);
+        if (ck.predicate == 9733 && T == 9217 && D == 9217) {  // :174-177, the one case that runs regex_match
+            if (!progs)
+                return fail(HDX_E_BADTYPE, "check %u: REGEX on a STRING attribute needs the compiled form", i);
+            if (*nprogs == HDX_MAX_REGEX_CHECKS)
+                return fail(HDX_E_INVALID, "more than %d REGEX checks on STRING attributes", HDX_MAX_REGEX_CHECKS);
+            if (!regex_parse(ck.value, ck.value_len, &progs[*nprogs]))
+                return fail(HDX_E_INVALID, "check %u: a pattern of more than %d items", i, HDX_REGEX_ITEMS_MAX);
+            o.attr = (uint16_t)ck.attr;
+            o.op = OP_REGEX;
+            o.family = FAM_STRING;
+            o.klen = (uint32_t)ck.value_len;
+            o.koff = (*nprogs)++;
+            continue;
+        }
         // :128-134 lookup(D) == NULL -> false.  A container, document or macaroon D is false too,
         // whichever way its validate(k) goes: T is primitive here, so T == D (:155-173) fails, the
         // LENGTH forms want D == INT64 (:182-199), REGEX wants D == STRING (:175), and a primitive
@@ -206,4 +225,28 @@ inline bool check_relation(uint8_t op, int cmp) {
     }
 }
 
+// regex_match(k, v) on the host with k's program; table: its byte classes
+// (regex_class of every byte), or NULL to work them out per byte of v.
+inline bool regex_run_host(const RegexProg& g, const uint64_t* table, const uint8_t* v, uint64_t len) {
+    uint64_t s = regex_start(g);
+    if (regex_accepted(g, s)) return true;
+    for (uint64_t i = 0; i < len; ++i) {
+        s = regex_step(g, s, table ? table[v[i]] : regex_class(g, v[i]));
+        if (regex_accepted(g, s)) return true;
+        if (!s) return false;  // anchored, and every position has died
+    }
+    return regex_at_end(g, s);
+}
+
 }  // namespace hdx
+
+// A compiled list of checks (hdx_checks_compile, hdx_cpu.cpp): one heap block,
+// host memory only, never written after compile — any thread, any device.
+struct hdx_checks_s {
+    uint32_t attrs_sz, c, nrx, pad_;
+    const uint32_t* types;                        // [attrs_sz], behind the struct
+    hdx_attribute_check checks[HDX_MAX_CHECKS];   // value: into the block
+    hdx::CheckOp ops[HDX_MAX_CHECKS];
+    hdx::RegexProg progs[HDX_MAX_REGEX_CHECKS];   // op k's: progs[ops[k].koff]
+    uint64_t table[HDX_MAX_REGEX_CHECKS][256];    // the host form's byte classes
+};

@@ -268,11 +268,21 @@ struct CheckArgs {
     CheckOp op[HDX_MAX_CHECKS];
     uint64_t konst[kCheckConstBytes / 8];
 };
+// The programs of a compiled list's OP_REGEX ops (op k's: prog[op[k].koff]):
+// a further, last kernel argument of the kernels that run them, so the kernels
+// the one-shot entry points launch keep their arguments.  Their byte-class tables
+// are built in LDS by each workgroup (hdx_check_eval.h).
+struct RegexArgs {
+    uint32_t count, pad_;
+    RegexProg prog[HDX_MAX_REGEX_CHECKS];
+};
 // check_kernel (the walk and the ops, a lane per object); with a.match also
 // one pass count per workgroup, their scan (scan_exclusive) and
 // check_compact_kernel.  The counts come from the library's stream-ordered
 // pool; if that allocation fails nothing is launched and *no_scratch is set.
-hipError_t launch_check_encoded(const CheckArgs& a, hipStream_t stream, bool* no_scratch);
+// rx: NULL, or a list with OP_REGEX ops (check_kernel<RegexArgs>).
+hipError_t launch_check_encoded(const CheckArgs& a, hipStream_t stream, bool* no_scratch,
+                                const RegexArgs* rx = nullptr);
 // The top-limit matches by one attribute (hdx_sorted.hip): the checks as
 // above (ck.first_fail may be NULL; ck.match is not used), then a 64-bit rank
 // key per matching object, a radix select of the limit-th key, the compacted
@@ -291,7 +301,9 @@ struct SortedArgs {
 // Device scratch of sorted_scratch_bytes(n) from the library's stream-ordered
 // pool; if that allocation fails nothing is launched and *no_scratch is set.
 uint64_t sorted_scratch_bytes(uint64_t n);
-hipError_t launch_sorted_search(const SortedArgs& a, hipStream_t stream, bool* no_scratch);
+hipError_t launch_sorted_search(const SortedArgs& a, hipStream_t stream, bool* no_scratch,
+                                const RegexArgs* rx = nullptr);
+static_assert(sizeof(SortedArgs) + sizeof(RegexArgs) + 64 <= 3072, "kernel arguments: well under the 4 KiB limit");
 // hdx_regions.hip: the library's per-device memory pool for stream-ordered
 // scratch (the regions' coordinate chunks and this scan's block sums), on the
 // calling thread's current device.

@@ -74,22 +74,29 @@ __device__ __forceinline__ uint64_t rank_float(uint64_t bits) {
     return (bits >> 63) ? ~bits : bits | 0x8000000000000000ull;
 }
 
-// Dynamic LDS: the checks' (check_lds_carve).
-__global__ void __launch_bounds__(kCheckBlock) sorted_rank_kernel(const SortedArgs a, uint64_t* rank,
-                                                                  uint8_t* member) {
+// Dynamic LDS: the checks' (check_lds_carve), for a list with OP_REGEX ops
+// their byte-class tables (regex_lds_bytes).  RXA: nothing — the one-shot
+// entry point's kernel, and a compiled list's without OP_REGEX ops — or
+// RegexArgs, a fourth kernel argument.
+template <typename... RXA>
+__global__ void __launch_bounds__(kCheckBlock) sorted_rank_kernel(const SortedArgs a, uint64_t* rank, uint8_t* member,
+                                                                  const RXA... rx) {
     extern __shared__ __attribute__((aligned(16))) uint64_t rank_lds[];
     constexpr uint32_t B = kCheckBlock;
+    constexpr bool RX = sizeof...(RXA) != 0;
     const CheckArgs& ck = a.ck;
     const uint32_t tid = threadIdx.x;
     uint32_t* end;
     const CheckLds s = check_lds_carve<B>(rank_lds, ck.c, &end);
+    RegexLds rl{};
     check_lds_init<B>(ck, s);
+    if constexpr (RX) regex_lds_init<B>(rl, rx..., end);
     const uint64_t i = (uint64_t)blockIdx.x * B + tid;
     bool badenc = false, badsize = false;
     if (i < ck.n) {
         uint32_t spos = 0, slen = 0;
         const uint32_t sattr = a.attr;
-        const uint32_t ff = check_object<B>(ck, s, i, [&](uint32_t j, uint32_t pos, uint32_t L) {
+        const uint32_t ff = check_object<B, RX>(ck, s, rl, i, [&](uint32_t j, uint32_t pos, uint32_t L) {
             if (j == sattr) {
                 spos = pos;
                 slen = L;
@@ -374,7 +381,7 @@ static uint64_t scratch_words(uint64_t n, uint64_t blocks) {
 
 uint64_t sorted_scratch_bytes(uint64_t n) { return scratch_words(n, (n + kCheckBlock - 1) / kCheckBlock) * 8; }
 
-hipError_t launch_sorted_search(const SortedArgs& a, hipStream_t stream, bool* no_scratch) {
+hipError_t launch_sorted_search(const SortedArgs& a, hipStream_t stream, bool* no_scratch, const RegexArgs* rx) {
     static_assert(HDX_SORT_LIMIT_MAX <= kSortFinishBlock, "the best so far fill half of the finishing sort's slots");
     static_assert(kHeadWords * 8 % 16 == 0, "the zeroed head");
     *no_scratch = false;
@@ -402,8 +409,12 @@ hipError_t launch_sorted_search(const SortedArgs& a, hipStream_t stream, bool* n
     const uint32_t grid = (uint32_t)blocks, hist_grid = (uint32_t)std::min<uint64_t>(blocks, kHistBlocks);
     e = hipMemsetAsync(base, 0, kHeadWords * 8, stream);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(sorted_rank_kernel, dim3(grid), dim3(kCheckBlock), check_lds_bytes(kCheckBlock, a.ck.c),
-                           stream, a, s.rank, s.member);
+        const size_t lds = check_lds_bytes(kCheckBlock, a.ck.c);
+        if (rx && rx->count)
+            hipLaunchKernelGGL(sorted_rank_kernel<RegexArgs>, dim3(grid), dim3(kCheckBlock),
+                               lds + regex_lds_bytes(rx->count), stream, a, s.rank, s.member, *rx);
+        else
+            hipLaunchKernelGGL(sorted_rank_kernel<>, dim3(grid), dim3(kCheckBlock), lds, stream, a, s.rank, s.member);
         e = hipGetLastError();
     }
     for (uint32_t p = 0; p < kPasses && e == hipSuccess; ++p) {

@@ -84,11 +84,23 @@ def sorted_search(types, keys, key_off, key_len, vals, val_off, val_len, checks:
     check_encoded): returns (first_fail i32[n] or None, top i64[count]).
     first_fail is check_encoded's; top holds the kept objects' indices in the
     output order.  The count is read back on `stream`, which is then waited for."""
+    t = np.ascontiguousarray(np.asarray(types, dtype=np.uint32))
+    arr = _checks(checks)
+
+    def call(ptrs, n, spec, lim, first_fail, top, count, status_ptr, stream_ptr):
+        return lib().hdx_sorted_search_device(t.ctypes.data, len(t), *ptrs, n, arr, len(checks), spec, lim,
+                                              first_fail, top, count, status_ptr, stream_ptr)
+    return _sorted_search(call, keys, key_off, key_len, vals, val_off, val_len, sort, limit, want_first_fail, status,
+                          stream)
+
+
+def _sorted_search(call, keys, key_off, key_len, vals, val_off, val_len, sort, limit, want_first_fail, status, stream):
+    """The tensors around one of the two device forms: call(the six pointers, n, sort, limit,
+    first_fail, top, count, status, stream) -> hdx_status."""
     import torch
 
     from .index import _torch_stream
 
-    t = np.ascontiguousarray(np.asarray(types, dtype=np.uint32))
     n = val_off.numel()
     dev = val_off.device
     for x in (keys, key_off, key_len, vals, val_off, val_len):
@@ -103,11 +115,9 @@ def sorted_search(types, keys, key_off, key_len, vals, val_off, val_len, checks:
     keys, key_off, key_len, vals, val_off, val_len = [x if x.numel() else count
                                                       for x in (keys, key_off, key_len, vals, val_off, val_len)]
     spec = sort._c()
-    check(lib().hdx_sorted_search_device(
-        t.ctypes.data, len(t), keys.data_ptr(), key_off.data_ptr(), key_len.data_ptr(), vals.data_ptr(),
-        val_off.data_ptr(), val_len.data_ptr(), n, _checks(checks), len(checks), ctypes.byref(spec), int(limit),
-        first_fail.data_ptr() if want_first_fail else None, top.data_ptr(), count.data_ptr(),
-        status.data_ptr() if status is not None else None, s.cuda_stream))
+    check(call([x.data_ptr() for x in (keys, key_off, key_len, vals, val_off, val_len)], n, ctypes.byref(spec),
+               int(limit), first_fail.data_ptr() if want_first_fail else None, top.data_ptr(), count.data_ptr(),
+               status.data_ptr() if status is not None else None, s.cuda_stream))
     with torch.cuda.stream(s):
         host = torch.empty(1, dtype=torch.int64, pin_memory=True)
         host.copy_(count, non_blocking=True)

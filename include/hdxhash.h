@@ -507,7 +507,8 @@ uint32_t hdx_index_scan_block(void);
  * Out of scope, HDX_E_BADTYPE before anything runs, in both forms: a check
  * with attr < attrs_sz whose attribute type is not STRING, INT64, FLOAT or
  * TIMESTAMP_* (the reference runs document_check, container length or
- * contains); REGEX where T == D == STRING (regex_match).  REGEX otherwise,
+ * contains); REGEX where T == D == STRING (regex_match: served by the
+ * compiled form, hdx_checks_compile below).  REGEX otherwise,
  * and any D on a primitive attribute, is simply false.  Also out of scope:
  * validate_attribute_checks, a host-resident (_host) pipeline, the device
  * set, check constants resident on the device. */
@@ -525,7 +526,8 @@ typedef struct hdx_attribute_check {
  * attribute k+1, k in [0, attrs_sz-1).  HDX_E_INVALID for a NULL pointer or
  * c > HDX_MAX_CHECKS, HDX_E_BADTYPE as above; *first_fail is then untouched.
  * The checks' values may have any size here (HDX_CHECK_BYTES_MAX is the
- * device form's). */
+ * device form's).  REGEX on a STRING attribute runs through the compiled form,
+ * hdx_checks_compile / hdx_checks_passes. */
 hdx_status hdx_passes_checks(const uint32_t* types, uint32_t attrs_sz,
                              const uint8_t* key, size_t key_len,
                              const uint8_t* const* values, const size_t* value_lens,
@@ -554,7 +556,8 @@ hdx_status hdx_passes_checks(const uint32_t* types, uint32_t attrs_sz,
  * hence the two caps).  With match, the compaction takes ~8 * (n / 256) bytes
  * from the library's per-device stream-ordered pool; if that fails nothing is
  * launched and the call returns HDX_E_NOMEM.  No kernel waits on another
- * workgroup, so match's order never varies. */
+ * workgroup, so match's order never varies.  REGEX on a STRING attribute runs
+ * through the compiled form, hdx_checks_compile / hdx_checks_encoded_device. */
 hdx_status hdx_check_encoded_device(const uint32_t* types, uint32_t attrs_sz,
                                     const uint8_t* keys, const uint64_t* key_off, const uint32_t* key_len,
                                     const uint8_t* vals, const uint64_t* val_off, const uint32_t* val_len,
@@ -634,7 +637,9 @@ hdx_status hdx_compare(uint32_t type, const uint8_t* a, size_t a_len, const uint
 /* The host form: stored objects in HOST memory, on the calling thread, any
  * limit (top has room for min(limit, n) indices); it allocates min(limit, n)
  * small records (HDX_E_NOMEM if it cannot).  *status (may be NULL) is ORed
- * into.  The checks' values may have any size. */
+ * into.  The checks' values may have any size.  REGEX on a STRING attribute
+ * is refused here as in hdx_passes_checks (the compiled form has no host
+ * sorted search). */
 hdx_status hdx_sorted_search(const uint32_t* types, uint32_t attrs_sz,
                              const uint8_t* keys, const uint64_t* key_off, const uint32_t* key_len,
                              const uint8_t* vals, const uint64_t* val_off, const uint32_t* val_len,
@@ -654,7 +659,9 @@ hdx_status hdx_sorted_search(const uint32_t* types, uint32_t attrs_sz,
  * boundary prefix shared by very many strings makes that step long, never
  * wrong.  Scratch: 17 * n + 16 * (n / 256) bytes and 17 KiB from the
  * library's per-device stream-ordered pool; if that allocation fails the call
- * returns HDX_E_NOMEM and launches nothing.  HDX_E_DEVICE without a device. */
+ * returns HDX_E_NOMEM and launches nothing.  HDX_E_DEVICE without a device.
+ * REGEX on a STRING attribute runs through the compiled form,
+ * hdx_checks_compile / hdx_checks_sorted_device. */
 hdx_status hdx_sorted_search_device(const uint32_t* types, uint32_t attrs_sz,
                                     const uint8_t* keys, const uint64_t* key_off, const uint32_t* key_len,
                                     const uint8_t* vals, const uint64_t* val_off, const uint32_t* val_len,
@@ -664,6 +671,73 @@ hdx_status hdx_sorted_search_device(const uint32_t* types, uint32_t attrs_sz,
                                     uint32_t* status_dev, hdx_stream stream);
 /* Candidates the finishing step takes per round (tests stand on it). */
 uint32_t hdx_sort_finish_block(void);
+
+/* ---- a list of checks compiled once per search: REGEX on STRING ----------- */
+
+/* The one check the one-shot forms above refuse, HYPERPREDICATE_REGEX with
+ * T == D == STRING (common/attribute_check.cc:174-177: regex_match(k, v),
+ * common/regex_match.cc), runs through a list of checks compiled once per
+ * search into a handle and then applied per object or per batch.  The
+ * reference's matcher recurses and backtracks (a.*a.*a.*b against 400 x 'a'
+ * takes seconds); the language it accepts is regular, and the forms here run
+ * a set-of-positions simulation whose time is linear in the text whatever the
+ * pattern.  After an optional leading '^' the pattern is read left to right
+ * into items:
+ *   \c                   LIT(c)       a trailing lone \    DEAD: matches nothing
+ *   x*                   STAR(x): .* is STAR(any); x may be ^, $ or *; \c* is
+ *                        LIT(c) followed by whatever * starts
+ *   $ as the last byte   END: true iff the text is used up
+ *   .                    ANY          anything else        LIT, bytes >= 0x80 included
+ * When the items run out the match succeeds whatever text remains; without ^
+ * every start position up to and including the text's end is tried; an empty
+ * pattern matches everything. */
+#define HDX_REGEX_ITEMS_MAX 63        /* items of one pattern: the states fit one 64-bit word */
+#define HDX_MAX_REGEX_CHECKS 4        /* REGEX-on-STRING checks per compiled list */
+
+/* regex_match(regex, text) of common/regex_match.cc on the host CPU: no
+ * device, no allocation, time linear in text_len whatever the pattern.
+ * *matched = 0 or 1.  HDX_E_INVALID for a NULL pointer or a pattern of more
+ * than HDX_REGEX_ITEMS_MAX items; *matched is then untouched. */
+hdx_status hdx_regex_match(const uint8_t* regex, size_t regex_len,
+                           const uint8_t* text, size_t text_len, int* matched);
+
+/* A compiled list of checks: host memory only.  It copies `types` and the
+ * checks with their bytes (the caller keeps nothing alive), holds no device
+ * memory and no per-device state, and may be used from several threads at
+ * once and on any device; hdx_checks_free(NULL) is legal.
+ * hdx_checks_compile applies every rule of hdx_check_encoded_device's compile
+ * step — the same HDX_E_INVALID (NULL pointers, c > HDX_MAX_CHECKS, more than
+ * HDX_CHECK_BYTES_MAX bytes of check values, patterns included) and the same
+ * HDX_E_BADTYPE for container and document attributes — with one exception:
+ * REGEX where T == D == STRING becomes regex_match(check.value, attribute).
+ * REGEX otherwise stays simply false.  HDX_E_INVALID also for more than
+ * HDX_MAX_REGEX_CHECKS such checks or a pattern of more than
+ * HDX_REGEX_ITEMS_MAX items (those searches stay on the daemon's loop, like
+ * the other caps); HDX_E_NOMEM; *out is then untouched. */
+typedef struct hdx_checks_s* hdx_checks;
+hdx_status hdx_checks_compile(const uint32_t* types, uint32_t attrs_sz,
+                              const hdx_attribute_check* checks, uint32_t c, hdx_checks* out);
+void       hdx_checks_free(hdx_checks);
+/* As hdx_passes_checks over the handle's types and checks. */
+hdx_status hdx_checks_passes(hdx_checks, const uint8_t* key, size_t key_len,
+                             const uint8_t* const* values, const size_t* value_lens,
+                             uint32_t* first_fail);
+/* As hdx_check_encoded_device and hdx_sorted_search_device over the handle's
+ * types and checks: for a list without a REGEX-on-STRING check exactly their
+ * outputs.  A list with one builds a 2 KiB byte-class table per such check in
+ * the workgroup's LDS from the kernel arguments: no device allocation, no
+ * upload. */
+hdx_status hdx_checks_encoded_device(hdx_checks,
+                                     const uint8_t* keys, const uint64_t* key_off, const uint32_t* key_len,
+                                     const uint8_t* vals, const uint64_t* val_off, const uint32_t* val_len,
+                                     uint64_t n, uint32_t* first_fail, uint64_t* match, uint64_t* match_count,
+                                     uint32_t* status_dev, hdx_stream stream);
+hdx_status hdx_checks_sorted_device(hdx_checks,
+                                    const uint8_t* keys, const uint64_t* key_off, const uint32_t* key_len,
+                                    const uint8_t* vals, const uint64_t* val_off, const uint32_t* val_len,
+                                    uint64_t n, const hdx_sort_spec* sort, uint64_t limit,
+                                    uint32_t* first_fail, uint64_t* top, uint64_t* top_count,
+                                    uint32_t* status_dev, hdx_stream stream);
 
 /* One range of a search, as range_searches() leaves it (common/range.h:40-55,
  * common/range_searches.cc:151-202): inclusive, at most one per attribute. */
