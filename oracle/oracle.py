@@ -14,6 +14,7 @@ _LIB = None
 _REF = None
 _REF_HASH = None
 _REF_STORE = None
+_REF_CHECKS = None
 
 
 def build():
@@ -123,6 +124,63 @@ def ref_store_lib():
         R.ref_partition.restype = ctypes.c_int
         _REF_STORE = R
     return _REF_STORE
+
+
+def ref_checks():
+    """oracle/_ref/libref_checks.so (the reference's common/attribute_check.cc over
+    its datatype_{string,int64,float,timestamp}.cc and regex_match.cc, behind
+    ref_checks_glue.cc), or None."""
+    global _REF_CHECKS
+    if _REF_CHECKS is None:
+        path = os.path.join(_HERE, "_ref", "libref_checks.so")
+        if not os.path.exists(path):
+            return None
+        R = ctypes.CDLL(path)
+        u64, u32, vp, sz = ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t
+        R.ref_passes_attribute_check.argtypes = [u32, u32, u32, ctypes.c_char_p, sz, ctypes.c_char_p, sz]
+        R.ref_passes_attribute_check.restype = ctypes.c_int
+        R.ref_passes_attribute_checks.argtypes = [vp, u32, vp, vp, vp, vp, vp, u32, ctypes.c_char_p, u64, vp, vp]
+        R.ref_passes_attribute_checks.restype = u64
+        R.ref_compare.argtypes = [u32, ctypes.c_char_p, sz, ctypes.c_char_p, sz, ctypes.POINTER(ctypes.c_int)]
+        R.ref_compare.restype = ctypes.c_int
+        R.ref_validate.argtypes = [u32, ctypes.c_char_p, sz]
+        R.ref_validate.restype = ctypes.c_int
+        _REF_CHECKS = R
+    return _REF_CHECKS
+
+
+def ref_passes_attribute_check(T: int, D: int, predicate: int, k: bytes, v: bytes) -> bool:
+    """The reference's passes_attribute_check(T, {k, D, predicate}, v)."""
+    return bool(ref_checks().ref_passes_attribute_check(T, D, predicate, k, len(k), v, len(v)))
+
+
+def ref_passes_attribute_checks(types, checks, key: bytes, values) -> int:
+    """The reference's passes_attribute_checks over a schema of `types`:
+    checks = [(attr < 65536, value bytes, datatype, predicate)], values = the
+    len(types) - 1 attributes after the key.  The index of the first failing
+    check, len(checks) when all pass."""
+    types = np.ascontiguousarray(types, np.uint32)
+    assert len(values) == len(types) - 1
+    c, m = len(checks), len(values)
+    attr = np.array([ck[0] for ck in checks] or [0], np.uint16)
+    dtype = np.array([ck[2] for ck in checks] or [0], np.uint32)
+    pred = np.array([ck[3] for ck in checks] or [0], np.uint32)
+    kval = (ctypes.c_char_p * max(c, 1))(*[bytes(ck[1]) for ck in checks])
+    klen = np.array([len(ck[1]) for ck in checks] or [0], np.uint64)
+    vals = (ctypes.c_char_p * max(m, 1))(*[bytes(v) for v in values])
+    vlen = np.array([len(v) for v in values] or [0], np.uint64)
+    return int(ref_checks().ref_passes_attribute_checks(
+        types.ctypes.data, len(types), attr.ctypes.data, dtype.ctypes.data, pred.ctypes.data, kval, klen.ctypes.data, c,
+        bytes(key), len(key), vals, vlen.ctypes.data))
+
+
+def ref_compare(type_id: int, a: bytes, b: bytes):
+    """The sign of the reference's datatype_info::lookup(type)->compare(a, b) ->
+    (sign, err); err 1: not a comparable type of the nine, 2: a numeric operand
+    neither empty nor 8 bytes (the reference asserts, so the glue refuses it)."""
+    sign = ctypes.c_int(0)
+    err = ref_checks().ref_compare(type_id, a, len(a), b, len(b), ctypes.byref(sign))
+    return sign.value, err
 
 
 def ref_decode_value(vals, off=0, length=None, max_attrs=None):

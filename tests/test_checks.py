@@ -4,8 +4,11 @@ passes_attribute_checks of common/attribute_check.cc:123-237 per object and over
 Expected values come from the restatement held here (`check_one`, `expected_first_fail`): Python
 `bytes` ordering for strings (unsigned, the shorter of two equal prefixes first: memcmp, then the
 lengths), `struct` for the numerics with the NaN rule written out.  Slices and decode verdicts of
-stored objects are the oracle's decode_value.  The restatement is unpinned: no committed recipe
-compiles attribute_check.cc."""
+stored objects are the oracle's decode_value.  The restatement is pinned for the primitive datatypes:
+tests/test_reference_checks.py holds `check_one`, `expected_first_fail` and `compare` to what the
+reference's compiled attribute_check.cc and datatype_*::compare return
+(tests/golden/reference_check_values.json).  A container, document or macaroon datatype in a
+check stays as restated."""
 import ctypes
 import os
 import shutil

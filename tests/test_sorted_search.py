@@ -9,7 +9,9 @@ Two restatements live here; the pools, `compare` and `expected_first_fail` are t
              __lt__(a, b) is the reference's operator<(b, a), popped when over `limit`, then a sort by the
              reference's operator>.  The reference's order among ties is unspecified, so R2 is compared by
              the sequence of sort values under compare == 0.
-Both are unpinned: no committed recipe compiles search_manager.cc, which needs the whole daemon."""
+R1's `compare` is pinned to the reference's compiled datatype_*::compare by tests/test_reference_checks.py
+(`sort_compare` wherever no NaN is involved; the NaN rule is the library's own).  R2 is unpinned: no
+committed recipe compiles search_manager.cc, which needs the whole daemon."""
 import ctypes
 import functools
 import heapq
