@@ -121,9 +121,10 @@ constexpr size_t check_lds_bytes(uint32_t B, uint32_t c) { return kCheckConstByt
 // kernel arguments and writes over all of the workgroup's LDS (the hardware
 // drops what lies past the allocation).  The results do not depend on it: the
 // constants' own words are right, and off / len are cleared afterwards.
-// Reading the ops as aligned dwords removes it, but measured 0.24-0.5 ms
-// slower per 10 M objects than this form for a reason not found, so it is left
-// to a change of its own.
+// Reading the ops as aligned dwords, or taking the count from the host,
+// removes it but is slower than this form: the overrun keeps part of the waves
+// off the walk, which then fetches fewer lines twice, so it
+// stays until the walk's rate no longer depends on it.
 template <uint32_t B>
 __device__ __forceinline__ void check_lds_init(const CheckArgs& a, const CheckLds& s) {
     const uint32_t c = a.c, tid = threadIdx.x;

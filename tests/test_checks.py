@@ -698,3 +698,60 @@ def test_gpu_offsets_across_4gib(torch_gpu):
     finally:
         arena.view = arena.arena = None
         torch.cuda.empty_cache()
+
+
+# ---- 9. the packed constants at their largest size -------------------------------------------------
+
+CAP_TYPES = [STRING, STRING, STRING]
+CAP_STORED = bytes((11 * i + 70) & 0xff for i in range(64)) + b"\x80"  # attribute 2 of every object
+CAP_LAST = bytes((5 * i + 0x41) & 0xff for i in range(49))              # check 15's constant
+CAP_N = 257                                                             # two workgroups, one lane in the second
+
+
+def cap_list():
+    """16 STRING comparisons whose constants, of lengths = 1 (mod 8), sum to HDX_CHECK_BYTES_MAX: packed,
+    each takes 7 bytes of padding, the largest block there is (1136 bytes).  Checks 0-14 compare attribute
+    2 with constants that differ from CAP_STORED in the last byte only, the predicates chosen so that all
+    pass: a lane reads every staged word of theirs.  Check 15: attribute 1 EQUALS CAP_LAST, whose last
+    byte lies alone in the block's last word."""
+    cl = []
+    for i in range(15):
+        above = i % 2 == 0
+        k = CAP_STORED[:64] + bytes([0x80 + (1 + i if above else -1 - i)])
+        cl.append(AttributeCheck(2, k, STRING, ((LT, LE) if above else (GT, GE))[i // 2 % 2]))
+    return cl + [AttributeCheck(1, CAP_LAST, STRING, EQ)]
+
+
+def cap_objects():
+    """Attribute 1 in turn: CAP_LAST, CAP_LAST with another last byte, CAP_LAST without its last byte."""
+    a1 = (CAP_LAST, CAP_LAST[:48] + bytes([CAP_LAST[48] ^ 1]), CAP_LAST[:48])
+    return [(b"key%d" % i, [a1[i % 3], CAP_STORED]) for i in range(CAP_N)]
+
+
+def assert_cap_outcomes(want, c):
+    """first_fail is c for a third of the objects and c - 1 for the rest: each outcome over a tenth."""
+    assert set(want.tolist()) == {c - 1, c}
+    assert np.array_equal(want == c, np.arange(CAP_N) % 3 == 0)
+    assert (want == c).mean() >= 0.10 and (want != c).mean() >= 0.10
+
+
+def test_cap_list_holds_both_outcomes():
+    """The condition of test_gpu_constants_at_the_cap, on the restatement alone; and the per-object form."""
+    cl, objs = cap_list(), cap_objects()
+    assert len(cl) == hdx.checks.HDX_MAX_CHECKS and all(len(ck.value) % 8 == 1 for ck in cl)
+    assert sum(len(ck.value) for ck in cl) == hdx.checks.HDX_CHECK_BYTES_MAX
+    want = np.array([expected_first_fail(CAP_TYPES, k, vs, cl) for k, vs in objs], np.uint32)
+    assert_cap_outcomes(want, 16)
+    assert [hdx.passes_checks(CAP_TYPES, k, vs, cl) for k, vs in objs] == want.tolist()
+
+
+@pytest.mark.gpu
+def test_gpu_constants_at_the_cap(torch_gpu):
+    """Every word of the largest constants block reaches the workgroups: a count one word short leaves
+    check 15's last byte unstaged, and the objects that equal CAP_LAST fail it."""
+    cl, objs = cap_list(), cap_objects()
+    want = np.array([expected_first_fail(CAP_TYPES, k, vs, cl) for k, vs in objs], np.uint32)
+    d = to_dev(torch_gpu, encode(CAP_TYPES, objs, "keycol"))
+    got = run(torch_gpu, CAP_TYPES, d, cl)
+    assert_result(got, want, 16)
+    assert int(got[1].size) == int((want == 16).sum()) == 86  # match_count: every third object of 257

@@ -487,6 +487,31 @@ def edge_patterns():
     return [p for p in gen.EDGE_PATTERNS if item_count(p) <= 63]
 
 
+def cap_lists():
+    """test_checks.cap_list, the largest block of packed constants, and the same with a '^'-anchored REGEX
+    op in place of check 0 (a list holds 16 checks at most): its table shares the workgroup's LDS with the
+    staged constants, which all move down by one 72-byte slot; that block is 1 064 bytes, 72 short of the
+    largest, and check 15's last byte still lies alone in its last word."""
+    from test_checks import CAP_LAST, cap_list
+    assert not set(CAP_LAST[:4]) & set(b".*\\$^")
+    return {"cap": cap_list(), "cap_regex": [rx(1, b"^" + CAP_LAST[:4])] + cap_list()[1:]}
+
+
+def cap_want(cl):
+    from test_checks import CAP_TYPES, cap_objects
+    return np.array([expected_first_fail(CAP_TYPES, k, vs, cl) for k, vs in cap_objects()], np.uint32)
+
+
+def test_cap_lists_hold_both_outcomes():
+    """The condition of test_gpu_constants_at_the_cap, on the restatement alone; and the host form."""
+    from test_checks import CAP_TYPES, assert_cap_outcomes, cap_objects
+    for name, cl in cap_lists().items():
+        want = cap_want(cl)
+        assert_cap_outcomes(want, 16)
+        with CompiledChecks(CAP_TYPES, cl) as cc:
+            assert [cc.passes(k, vs) for k, vs in cap_objects()] == want.tolist(), name
+
+
 @pytest.fixture(scope="module")
 def torch_gpu():
     import torch
@@ -560,6 +585,21 @@ def test_gpu_bad_encodings(torch_gpu):
         got = run(torch_gpu, cc, s.dev(torch_gpu, val_len=val_len))
     assert_result(got, want, 2, want_status=BADENC_BIT)
     assert not set(got[1].tolist()) & set(bad.tolist()) and len(got[1]) > 0
+
+
+@pytest.mark.gpu
+def test_gpu_constants_at_the_cap(torch_gpu):
+    """test_checks.test_gpu_constants_at_the_cap through a compiled list, without and with a REGEX op ahead
+    of the STRING comparisons.  One launch per list: a second one could find the first one's words still
+    in LDS."""
+    from test_checks import CAP_TYPES, cap_objects, encode, to_dev
+    d = to_dev(torch_gpu, encode(CAP_TYPES, cap_objects(), "keycol"))
+    for name, cl in cap_lists().items():
+        want = cap_want(cl)
+        with CompiledChecks(CAP_TYPES, cl) as cc:
+            got = run(torch_gpu, cc, d)
+        assert_result(got, want, 16)
+        assert int(got[1].size) == int((want == 16).sum()) == 86, name
 
 
 def sort_key(obj, attr):
