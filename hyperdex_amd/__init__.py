@@ -18,6 +18,8 @@ from .index import (IndexSpec, index_encode, index_entries, index_entries_fill, 
                     index_entry, index_key_size, search_regions, search_space)
 from .checks import AttributeCheck, CompiledChecks, check_encoded, passes_checks, regex_match  # noqa: F401
 from .sorting import SortSpec, compare, sorted_search, sorted_search_host  # noqa: F401
+from .gather import (gather_objects, gather_objects_fill, gather_objects_host, gather_objects_plan,  # noqa: F401
+                     gather_tile_bytes)
 from .batcher import Batcher  # noqa: F401
 
 __all__ = ["HdxError", "Attribute", "Schema", "hash", "hash_key", "hash_object", "hash_batch",
@@ -26,4 +28,6 @@ __all__ = ["HdxError", "Attribute", "Schema", "hash", "hash_key", "hash_object",
            "init_mask", "device_set", "shutdown", "hashable", "schema_check", "RegionTable",
            "lookup_region", "PointLeaders", "PointLeaderAbort", "index_encode", "index_key_size", "IndexSpec", "index_entry",
            "index_entries", "index_entries_plan", "index_entries_fill", "search_regions", "search_space", "AttributeCheck",
-           "passes_checks", "check_encoded", "CompiledChecks", "regex_match", "SortSpec", "compare", "sorted_search", "sorted_search_host", "Batcher", "lib"]
+           "passes_checks", "check_encoded", "CompiledChecks", "regex_match", "SortSpec", "compare", "sorted_search", "sorted_search_host",
+           "gather_objects", "gather_objects_plan", "gather_objects_fill", "gather_objects_host", "gather_tile_bytes",
+           "Batcher", "lib"]

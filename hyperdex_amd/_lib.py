@@ -114,6 +114,11 @@ SIGNATURES = [
     ("hdx_checks_encoded_device", _i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp]),
     ("hdx_checks_sorted_device", _i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp,
                                         _vp]),
+    ("hdx_gather_objects_plan_device", _i32, [_vp, _vp, _u64, _vp, _vp, _u64, _u32, _vp, _vp, _vp, _vp]),
+    ("hdx_gather_objects_fill_device", _i32, [_vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _u32, _vp, _vp,
+                                              _u64, _vp, _vp]),
+    ("hdx_gather_tile_bytes", _u32, []),
+    ("hdx_gather_objects", _i32, [_vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _u64, _u32, _vp, _vp, _vp, _u64, _vp]),
     ("hdx_search_regions", _i32, [_vp, _vp, _u32, _vp, _vp, _vp]),
     ("hdx_search_space", _i32, [_vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp, _vp]),
     ("hdx_batcher_create", _i32, [_vp, _u32, _vp, _vp]),
@@ -137,6 +142,8 @@ DEBUG_SIGNATURES = [
     ("hdxdbg_kernel_variant", _i32, []),
     ("hdxdbg_variant_entries", _i32, [_i32]),
     ("hdxdbg_init_devices", _i32, [_vp, _i32]),
+    ("hdxdbg_gather_objects_fill_by_extents", _i32, [_vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _u32, _vp,
+                                                     _vp, _u64, _vp, _vp]),
 ]
 
 _LIB = None

@@ -349,6 +349,100 @@ HDX_EXPORT hdx_status hdx_checks_sorted_device(hdx_checks h, const uint8_t* keys
                              val_len, n, sort, limit, first_fail, top, top_count, status_dev, stream);
 }
 
+// ---- the objects behind a match or top list (hdx_gather_objects.hip) --------
+
+HDX_EXPORT uint32_t hdx_gather_tile_bytes(void) { return kGatherTileBytes; }
+
+namespace {
+
+// Fill's arguments, checked; both fill forms take them.
+hdx_status gather_fill_args(GatherObjectsArgs& a, const uint8_t* keys, const uint64_t* key_off,
+                            const uint32_t* key_len, const uint8_t* vals, const uint64_t* val_off,
+                            const uint32_t* val_len, uint64_t n, const uint64_t* idx, const uint64_t* count_dev,
+                            uint64_t cap, uint32_t what, const uint64_t* rec_off, uint8_t* out, uint64_t out_bytes,
+                            uint32_t* status_dev) {
+    hdx_status st = gather_objects_check(key_len && val_len && idx && rec_off && out, true, keys, key_off, vals,
+                                         val_off, n, cap, what);
+    if (st != HDX_OK) return st;
+    if ((st = bind_device(-1)) != HDX_OK) return st;
+    a = GatherObjectsArgs{};
+    a.keys = keys;
+    a.key_off = key_off;
+    a.key_len = key_len;
+    a.vals = vals;
+    a.val_off = val_off;
+    a.val_len = val_len;
+    a.idx = idx;
+    a.count = count_dev;
+    a.rec_off = const_cast<uint64_t*>(rec_off);
+    a.out = out;
+    a.out_bytes = out_bytes;
+    a.status = status_dev;
+    a.n = n;
+    a.cap = cap;
+    a.what = what;
+    return HDX_OK;
+}
+
+}  // namespace
+
+HDX_EXPORT hdx_status hdx_gather_objects_plan_device(const uint32_t* key_len, const uint32_t* val_len, uint64_t n,
+                                                     const uint64_t* idx, const uint64_t* count_dev, uint64_t cap,
+                                                     uint32_t what, uint64_t* rec_off, uint32_t* rec_key_len,
+                                                     uint32_t* status_dev, hdx_stream stream) {
+    hdx_status st = gather_objects_check(key_len && val_len && idx && rec_off, false, nullptr, nullptr, nullptr,
+                                         nullptr, n, cap, what);
+    if (st != HDX_OK) return st;
+    if ((st = bind_device(-1)) != HDX_OK) return st;
+    GatherObjectsArgs a{};
+    a.key_len = key_len;
+    a.val_len = val_len;
+    a.idx = idx;
+    a.count = count_dev;
+    a.rec_off = rec_off;
+    a.rec_key_len = rec_key_len;
+    a.status = status_dev;
+    a.n = n;
+    a.cap = cap;
+    a.what = what;
+    bool no_scratch = false;
+    HIP_TRY(launch_gather_objects_plan(a, (hipStream_t)stream, &no_scratch));
+    if (no_scratch) return fail(HDX_E_NOMEM, "scan scratch for %llu records", (unsigned long long)cap);
+    return HDX_OK;
+}
+
+HDX_EXPORT hdx_status hdx_gather_objects_fill_device(const uint8_t* keys, const uint64_t* key_off,
+                                                     const uint32_t* key_len, const uint8_t* vals,
+                                                     const uint64_t* val_off, const uint32_t* val_len, uint64_t n,
+                                                     const uint64_t* idx, const uint64_t* count_dev, uint64_t cap,
+                                                     uint32_t what, const uint64_t* rec_off, uint8_t* out,
+                                                     uint64_t out_bytes, uint32_t* status_dev, hdx_stream stream) {
+    GatherObjectsArgs a;
+    const hdx_status st = gather_fill_args(a, keys, key_off, key_len, vals, val_off, val_len, n, idx, count_dev, cap,
+                                           what, rec_off, out, out_bytes, status_dev);
+    if (st != HDX_OK) return st;
+    HIP_TRY(launch_gather_objects_fill(a, (hipStream_t)stream));
+    return HDX_OK;
+}
+
+#if HDX_DEBUG_BUILD
+HDX_EXPORT int hdxdbg_gather_objects_fill_by_extents(const uint8_t* keys, const uint64_t* key_off,
+                                                     const uint32_t* key_len, const uint8_t* vals,
+                                                     const uint64_t* val_off, const uint32_t* val_len, uint64_t n,
+                                                     const uint64_t* idx, const uint64_t* count_dev, uint64_t cap,
+                                                     uint32_t what, const uint64_t* rec_off, uint8_t* out,
+                                                     uint64_t out_bytes, uint32_t* status_dev, void* stream) {
+    GatherObjectsArgs a;
+    const hdx_status st = gather_fill_args(a, keys, key_off, key_len, vals, val_off, val_len, n, idx, count_dev, cap,
+                                           what, rec_off, out, out_bytes, status_dev);
+    if (st != HDX_OK) return st;
+    bool no_scratch = false;
+    HIP_TRY(launch_gather_objects_by_extents(a, (hipStream_t)stream, &no_scratch));
+    if (no_scratch) return fail(HDX_E_NOMEM, "extents of %llu records", (unsigned long long)cap);
+    return HDX_OK;
+}
+#endif
+
 HDX_EXPORT hdx_status hdx_search_regions(hdx_region_table t, const hdx_range* ranges, uint32_t nranges,
                                          const uint8_t* has_replicas, uint8_t* include, int* cleared) {
     if (!t || !cleared || (nranges && !ranges) || (t->R && !include))

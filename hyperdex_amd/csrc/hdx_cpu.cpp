@@ -600,3 +600,49 @@ HDX_EXPORT hdx_status hdx_sorted_search(const uint32_t* types, uint32_t attrs_sz
     if (status) *status |= bits;
     return HDX_OK;
 }
+
+// The objects behind a list of indices, packed (the host form of
+// hdx_gather_objects_plan_device / _fill_device): the offsets first, since
+// nothing may be written when they do not fit, then the bytes.
+HDX_EXPORT hdx_status hdx_gather_objects(const uint8_t* keys, const uint64_t* key_off, const uint32_t* key_len,
+                                         const uint8_t* vals, const uint64_t* val_off, const uint32_t* val_len,
+                                         uint64_t n, const uint64_t* idx, uint64_t count, uint32_t what,
+                                         uint64_t* rec_off, uint32_t* rec_key_len, uint8_t* out, uint64_t out_bytes,
+                                         uint32_t* status) {
+    const hdx_status st = gather_objects_check(key_len && val_len && idx && rec_off && out, true, keys, key_off, vals,
+                                               val_off, n, count, what);
+    if (st != HDX_OK) return st;
+    uint32_t bits = 0;
+    uint64_t at = 0;
+    for (uint64_t r = 0; r < count; ++r) {
+        const uint64_t i = idx[r];
+        uint32_t kl = 0;
+        uint64_t size = 0;
+        if (i < n) {
+            if (what & HDX_GATHER_KEYS) kl = key_len[i];
+            size = (uint64_t)kl + ((what & HDX_GATHER_VALUES) ? val_len[i] : 0u);
+        } else {
+            bits |= 1u << HDX_E_INVALID;
+        }
+        rec_off[r] = at;
+        if (rec_key_len) rec_key_len[r] = kl;
+        at += size;
+    }
+    rec_off[count] = at;
+    if (at > out_bytes) {
+        if (status) *status |= bits | (1u << HDX_E_NOMEM);
+        return fail(HDX_E_NOMEM, "records of %llu bytes, room for %llu", (unsigned long long)at,
+                    (unsigned long long)out_bytes);
+    }
+    for (uint64_t r = 0; r < count; ++r) {
+        const uint64_t size = rec_off[r + 1] - rec_off[r];
+        if (size == 0) continue;  // an index >= n among them
+        const uint64_t i = idx[r];
+        uint8_t* d = out + rec_off[r];
+        const uint32_t kl = (what & HDX_GATHER_KEYS) ? key_len[i] : 0;
+        if (kl) memcpy(d, keys + key_off[i], kl);
+        if (size > kl) memcpy(d + kl, vals + val_off[i], size - kl);
+    }
+    if (status) *status |= bits;
+    return HDX_OK;
+}

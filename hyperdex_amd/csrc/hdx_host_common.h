@@ -70,6 +70,26 @@ inline uint64_t entry_encoded_size(uint32_t enc, uint64_t len) {
 // Sets the calling thread's hdx_last_error() text and returns s.
 hdx_status fail(hdx_status s, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 
+// What hdx_gather_objects and its two device calls refuse before anything is
+// read (include/hdxhash.h): `required` is the form's other pointers ANDed
+// together; keys and key_off matter only with KEYS, vals and val_off only
+// with VALUES (with_bytes: the forms that copy; the plan reads lengths only).
+constexpr uint64_t kGatherMaxRecords = 1ull << 40;
+inline hdx_status gather_objects_check(bool required, bool with_bytes, const void* keys, const void* key_off,
+                                       const void* vals, const void* val_off, uint64_t n, uint64_t cap,
+                                       uint32_t what) {
+    if (what == 0 || (what & ~(HDX_GATHER_KEYS | HDX_GATHER_VALUES)))
+        return fail(HDX_E_INVALID, "what=%u is not HDX_GATHER_KEYS, HDX_GATHER_VALUES or both", what);
+    if (!required) return fail(HDX_E_INVALID, "NULL pointer");
+    if (with_bytes && (what & HDX_GATHER_KEYS) && (!keys || !key_off))
+        return fail(HDX_E_INVALID, "HDX_GATHER_KEYS without keys or key_off");
+    if (with_bytes && (what & HDX_GATHER_VALUES) && (!vals || !val_off))
+        return fail(HDX_E_INVALID, "HDX_GATHER_VALUES without vals or val_off");
+    if (n > kGatherMaxRecords || cap > kGatherMaxRecords)
+        return fail(HDX_E_INVALID, "n=%llu or cap=%llu above 2^40", (unsigned long long)n, (unsigned long long)cap);
+    return HDX_OK;
+}
+
 // ---- a search's attribute checks (common/attribute_check.cc:123-237) --------
 //
 // One compiled form for the per-object CPU path (hdx_cpu.cpp) and the device

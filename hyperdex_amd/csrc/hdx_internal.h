@@ -248,6 +248,36 @@ hipError_t launch_index_entries_fill(const IndexEntriesArgs& a, hipStream_t stre
 hipError_t scan_exclusive(uint64_t* data, uint64_t N, uint64_t* scratch, hipStream_t stream);
 uint64_t scan_scratch_words(uint64_t N);
 
+// The objects behind a list of indices, packed (hdx_gather_objects.hip):
+// record r = [key of idx[r] if KEYS][value of idx[r] if VALUES] at out +
+// rec_off[r], r < min(*count, cap).
+constexpr uint32_t kGatherTileBytes = 4096;  // output bytes a wave of the fill owns per step
+struct GatherObjectsArgs {
+    const uint8_t* keys;      // fill only
+    const uint64_t* key_off;  // fill only
+    const uint32_t* key_len;
+    const uint8_t* vals;      // fill only
+    const uint64_t* val_off;  // fill only
+    const uint32_t* val_len;  // plan only
+    const uint64_t* idx;      // [cap]
+    const uint64_t* count;    // one u64, or NULL: cap
+    uint64_t* rec_off;        // [cap + 1] plan writes, fill reads
+    uint32_t* rec_key_len;    // [cap] plan only, may be NULL
+    uint8_t* out;             // fill only
+    uint64_t out_bytes;
+    uint32_t* status;         // may be NULL
+    uint64_t n, cap;
+    uint32_t what;            // HDX_GATHER_KEYS | HDX_GATHER_VALUES
+};
+// A lane per record stores its size, then scan_exclusive over cap + 1
+// elements; block sums from scratch_pool, *no_scratch as above.
+hipError_t launch_gather_objects_plan(const GatherObjectsArgs& a, hipStream_t stream, bool* no_scratch);
+// Tile-owned: a wave per kGatherTileBytes of the output.
+hipError_t launch_gather_objects_fill(const GatherObjectsArgs& a, hipStream_t stream);
+// Debug library only: the plan as two extents per record, then
+// launch_gather_extents (the record-major A/B baseline).
+hipError_t launch_gather_objects_by_extents(const GatherObjectsArgs& a, hipStream_t stream, bool* no_scratch);
+
 // A search's attribute checks over stored objects (hdx_checks.hip): the ops
 // of compile_checks (hdx_host_common.h) and their STRING constants, packed
 // at op[k].koff, travel by value.

@@ -614,8 +614,9 @@ uint32_t hdx_check_block_objects(void);
  * reserved != 0, and in the device form limit > HDX_SORT_LIMIT_MAX or more
  * than HDX_CHECK_BYTES_MAX bytes of check values.  The outputs are then
  * untouched.  Out of scope: a host-resident (_host) pipeline, the device set,
- * larger limits on the device, packing the kept objects into a response,
- * container or document sort attributes. */
+ * larger limits on the device, container or document sort attributes, the
+ * response's wire format (the kept objects themselves: hdx_gather_objects_*
+ * below). */
 #define HDX_SORT_LIMIT_MAX 1024
 #define HDX_KEEP_SMALLEST 0
 #define HDX_KEEP_LARGEST  1
@@ -738,6 +739,77 @@ hdx_status hdx_checks_sorted_device(hdx_checks,
                                     uint64_t n, const hdx_sort_spec* sort, uint64_t limit,
                                     uint32_t* first_fail, uint64_t* top, uint64_t* top_count,
                                     uint32_t* status_dev, hdx_stream stream);
+
+/* ---- the objects behind a match or top list, packed ----------------------- */
+
+/* What the daemon sends for a search is the objects themselves: key and value
+ * per item (search_manager::next, daemon/search_manager.cc:267-281), every
+ * kept item's key and value in one message (sorted_search, :484-501), each
+ * matching key (group_keyop, :505-560).  These calls turn a device list of
+ * object indices — `match` of hdx_check_encoded_device, `top` of
+ * hdx_sorted_search_device — into the objects' bytes packed back to back, in
+ * two calls so that the caller allocates the output between them.  The
+ * output is the library's own stored-object form, not the response's wire
+ * format (e::slice and the packing are libe's): nothing is decoded, so it
+ * goes back in one copy and is valid input to every *_encoded_device call.
+ *
+ * Stored objects as in hdx_hash_encoded_device (any placement and alignment,
+ * keys == vals records included), n of them.  idx[0 .. cap) is a DEVICE list
+ * of object indices in any order, duplicates allowed; count_dev one DEVICE
+ * u64 (match_count, top_count): the records are r < count = min(*count_dev,
+ * cap); with count_dev == NULL, count = cap.  Nothing is read back; both
+ * calls are asynchronous on `stream`.  `what`: HDX_GATHER_KEYS,
+ * HDX_GATHER_VALUES or both.
+ *
+ * Record r is [key of idx[r] if KEYS][value of idx[r] if VALUES], copied
+ * verbatim: a value keeps its version and count header.  Plan writes
+ *   rec_off[0 .. cap]     the exclusive prefix sum of the record sizes; for
+ *                         r >= count rec_off[r + 1] = rec_off[count], so
+ *                         rec_off[cap] is the total (as entry_off[n*m]);
+ *   rec_key_len[r]        (may be NULL) key_len[idx[r]] with KEYS, else 0;
+ *                         0 for r >= count.
+ * Over `out` they describe a stored-object batch of cap objects:
+ *   key_off' = rec_off[r]                  key_len' = rec_key_len[r]
+ *   val_off' = rec_off[r] + rec_key_len[r] val_len' = size - rec_key_len[r].
+ * idx[r] >= n gives a record of size 0 and (1u << HDX_E_INVALID) ORed into
+ * *status_dev (may be NULL); every other record is exact.
+ *
+ * Fill writes record r at out + rec_off[r] (out may have any alignment; only
+ * the records' own bytes are written, and none is read first).  If
+ * rec_off[cap] > out_bytes it writes nothing and ORs (1u << HDX_E_NOMEM) into
+ * *status_dev.  It takes the arguments plan took, and plan's rec_off.
+ *
+ * Before the device is touched: HDX_E_INVALID for a NULL pointer (status_dev,
+ * count_dev and rec_key_len may be NULL; keys and key_off only with KEYS,
+ * vals and val_off only with VALUES), `what` of 0 or with other bits set, cap
+ * or n above 2^40.  cap == 0 is legal: rec_off[0] = 0.  HDX_E_DEVICE without
+ * a device.  The plan's prefix sum takes ~8 * (cap / 1024) bytes from the
+ * library's per-device stream-ordered pool; if that fails nothing is launched
+ * and the call returns HDX_E_NOMEM.  No kernel waits on another workgroup and
+ * no atomic hands out positions: the output is the same on every run. */
+#define HDX_GATHER_KEYS   1u
+#define HDX_GATHER_VALUES 2u
+hdx_status hdx_gather_objects_plan_device(const uint32_t* key_len, const uint32_t* val_len, uint64_t n,
+                                          const uint64_t* idx, const uint64_t* count_dev, uint64_t cap,
+                                          uint32_t what, uint64_t* rec_off, uint32_t* rec_key_len,
+                                          uint32_t* status_dev, hdx_stream stream);
+hdx_status hdx_gather_objects_fill_device(const uint8_t* keys, const uint64_t* key_off, const uint32_t* key_len,
+                                          const uint8_t* vals, const uint64_t* val_off, const uint32_t* val_len,
+                                          uint64_t n, const uint64_t* idx, const uint64_t* count_dev, uint64_t cap,
+                                          uint32_t what, const uint64_t* rec_off, uint8_t* out, uint64_t out_bytes,
+                                          uint32_t* status_dev, hdx_stream stream);
+/* Output bytes one wave of the fill owns per step: a tile, cut at multiples
+ * of this from out's 16-byte-aligned base (tests stand on it). */
+uint32_t hdx_gather_tile_bytes(void);
+/* The same contract over HOST memory on the calling thread: no device, no
+ * allocation.  rec_off[count + 1], rec_key_len[count] (may be NULL); the bits
+ * are ORed into *status (may be NULL).  Returns HDX_E_NOMEM, with rec_off and
+ * rec_key_len filled and nothing written to out, when rec_off[count] >
+ * out_bytes; HDX_E_INVALID as above (count in cap's place). */
+hdx_status hdx_gather_objects(const uint8_t* keys, const uint64_t* key_off, const uint32_t* key_len,
+                              const uint8_t* vals, const uint64_t* val_off, const uint32_t* val_len, uint64_t n,
+                              const uint64_t* idx, uint64_t count, uint32_t what, uint64_t* rec_off,
+                              uint32_t* rec_key_len, uint8_t* out, uint64_t out_bytes, uint32_t* status);
 
 /* One range of a search, as range_searches() leaves it (common/range.h:40-55,
  * common/range_searches.cc:151-202): inclusive, at most one per attribute. */

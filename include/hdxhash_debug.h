@@ -8,7 +8,9 @@
  * hdxdbg_wave_geometry (tests/test_window_edges.py's window boundaries).
  * libhdxhash_dbg.so only (HDX_DEBUG_BUILD, hyperdex_amd/csrc/Makefile):
  * hdxdbg_set_kernel_variant / hdxdbg_kernel_variant / hdxdbg_variant_entries,
- * used by scripts/ab_variants.py and the variant parity tests.  The product library
+ * used by scripts/ab_variants.py and the variant parity tests, and
+ * hdxdbg_gather_objects_fill_by_extents, the object gather's record-major
+ * baseline.  The product library
  * has no kernel selection and no environment switches.
  */
 #ifndef HDXHASH_DEBUG_H
@@ -73,6 +75,18 @@ uint64_t hdxdbg_region_chunk_objects(uint64_t n, uint32_t attrs_sz);
  * included. */
 #define HDXDBG_WAVE_GEOMETRY_WORDS 7
 int hdxdbg_wave_geometry(const uint32_t* types, uint32_t attrs_sz, int sweep, uint32_t* out);
+/* [debug library only] hdx_gather_objects_fill_device's arguments and output
+ * by the record-major form: a kernel turns the plan into two extents per
+ * record (source address, length, destination offset), then the host
+ * pipelines' extent copy (hdx_gather.hip), a wave per extent, moves them.
+ * The A/B baseline of tools/gather_objects_rate.py and a second opinion for
+ * the tests.  The extents, 40 bytes per record, come from the library's
+ * stream-ordered pool (HDX_E_NOMEM, nothing launched, if that fails). */
+int hdxdbg_gather_objects_fill_by_extents(const uint8_t* keys, const uint64_t* key_off, const uint32_t* key_len,
+                                          const uint8_t* vals, const uint64_t* val_off, const uint32_t* val_len,
+                                          uint64_t n, const uint64_t* idx, const uint64_t* count_dev, uint64_t cap,
+                                          uint32_t what, const uint64_t* rec_off, uint8_t* out, uint64_t out_bytes,
+                                          uint32_t* status_dev, void* stream);
 
 #ifdef __cplusplus
 }
