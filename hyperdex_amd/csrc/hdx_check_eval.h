@@ -5,8 +5,8 @@
 //
 // Loads: numerics as one unaligned 8-byte value lying wholly inside the key
 // or attribute; strings in 8-byte steps the same way, and the last 1..7 bytes
-// as the aligned dwords that hold them (as seg_bytes of hdx_index_entries.hip
-// reads a segment's end) — never a dword that holds no byte of the attribute.
+// as the aligned dwords that hold them (word_bytes, hdx_wave.h) — never a
+// dword that holds no byte of the attribute.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -16,34 +16,11 @@
 
 #include "hdx_internal.h"
 #include "hdx_value_walk.h"
+#include "hdx_wave.h"
 
 namespace hdx {
 
-typedef uint32_t __attribute__((aligned(1))) ck_u32_u;
-typedef uint64_t __attribute__((aligned(1))) ck_u64_u;
-typedef const __attribute__((address_space(1))) ck_u32_u* ck_gu32_ptr;
-typedef const __attribute__((address_space(1))) ck_u64_u* ck_gu64_ptr;
-typedef const __attribute__((address_space(1))) uint32_t* ck_g32_ptr;
-
 constexpr uint32_t kKonstWords = kCheckConstBytes / 8;
-
-// The `take` (1..4) bytes at p in the low bytes of the result, the rest zero.
-__device__ __forceinline__ uint32_t tail_bytes(const uint8_t* p, uint32_t take) {
-    if (take == 4) return *(ck_gu32_ptr)p;
-    const uint32_t sh = (uint32_t)(uintptr_t)p & 3;
-    const uint8_t* q = p - sh;  // the aligned dword that holds p[0]
-    const uint32_t d0 = *(ck_g32_ptr)q;
-    const uint32_t d1 = sh + take > 4 ? *(ck_g32_ptr)(q + 4) : 0u;
-    return __builtin_amdgcn_alignbyte(d1, d0, sh) & ((1u << (8 * take)) - 1);
-}
-
-// The r (1..8) bytes at p as a little-endian word, zero-padded.
-__device__ __forceinline__ uint64_t word_bytes(const uint8_t* p, uint32_t r) {
-    if (r >= 8) return *(ck_gu64_ptr)p;
-    uint64_t b = tail_bytes(p, std::min(r, 4u));
-    if (r > 4) b |= (uint64_t)tail_bytes(p + 4, r - 4) << 32;
-    return b;
-}
 
 // compare(k, v) of datatype_string.cc:263-285, k in LDS at 8-byte-aligned kw
 // (zero-padded to 8): memcmp over the shorter length as big-endian unsigned
@@ -54,11 +31,10 @@ __device__ __forceinline__ int compare_string(const uint64_t* kw, uint32_t klen,
         const uint32_t r = m - w;
         uint64_t a = kw[w >> 3], b;
         if (r >= 8) {
-            b = *(ck_gu64_ptr)(v + w);
+            b = *(gu64_ptr)(v + w);
         } else {
             a &= (1ull << (8 * r)) - 1;  // k may go on past the shorter length
-            b = tail_bytes(v + w, std::min(r, 4u));
-            if (r > 4) b |= (uint64_t)tail_bytes(v + w + 4, r - 4) << 32;
+            b = word_bytes(v + w, r);
         }
         if (a != b) return __builtin_bswap64(a) < __builtin_bswap64(b) ? -1 : 1;
     }
@@ -78,7 +54,7 @@ __device__ __forceinline__ bool eval_op(const CheckOp& o, const uint64_t* s_kons
         cmp = compare_string(s_konst + (o.koff >> 3), o.klen, p, len);
     } else {
         if (len != 0 && len != 8) return false;  // :141 validate(v): fails every check, no status bit
-        const uint64_t vb = len ? *(ck_gu64_ptr)p : 0;  // an empty value is 0 / 0.0
+        const uint64_t vb = len ? *(gu64_ptr)p : 0;  // an empty value is 0 / 0.0
         if (o.family == FAM_INT64) {
             const int64_t k = (int64_t)o.imm, v = (int64_t)vb;
             cmp = k < v ? -1 : k > v ? 1 : 0;

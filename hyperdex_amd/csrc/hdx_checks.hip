@@ -11,9 +11,9 @@
 //            ops in order up to the first false one and stores first_fail.
 //            With compaction it also stores how many of its workgroup's
 //            objects pass.
-//   scan     scan_exclusive (hdx_index_entries.hip) over those counts.
+//   scan     scan_exclusive (hdx_scratch.hip) over those counts.
 //   compact  check_compact_kernel: the same workgroups re-read first_fail,
-//            rank the passing objects inside the workgroup (ballots) and
+//            rank the passing objects inside the workgroup (block_ranks) and
 //            store their indices at the workgroup's scanned base; the last
 //            workgroup stores the total.  No kernel waits on another
 //            workgroup, no atomic hands out positions: match is ascending.
@@ -56,16 +56,11 @@ __global__ void __launch_bounds__(kCheckBlock) check_kernel(const CheckArgs a, u
         pass = ff == c;
         a.first_fail[i] = ff;
     }
-    if (a.status && __any(badenc) && (tid & 63) == 0) atomicOr(a.status, 1u << 6 /* HDX_E_BADENC */);
+    wave_status_or(a.status, badenc, kStatusBadEnc);
     if (block_pass) {
-        const uint32_t cnt = (uint32_t)__popcll(__ballot(pass));
-        if ((tid & 63) == 0) s_cnt[tid >> 6] = cnt;
-        __syncthreads();
-        if (tid == 0) {
-            uint32_t all = 0;
-            for (uint32_t w = 0; w < B / 64; ++w) all += s_cnt[w];
-            block_pass[blockIdx.x] = all;
-        }
+        uint32_t rank[1], all[1];
+        block_ranks<B, 1>({pass}, s_cnt, rank, all);
+        if (tid == 0) block_pass[blockIdx.x] = all[0];
     }
 }
 
@@ -73,22 +68,14 @@ __global__ void __launch_bounds__(kCheckBlock) check_kernel(const CheckArgs a, u
 __global__ void __launch_bounds__(kCheckBlock) check_compact_kernel(const CheckArgs a, const uint64_t* block_base) {
     __shared__ uint32_t s_cnt[kCheckBlock / 64];
     constexpr uint32_t B = kCheckBlock;
-    const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const uint32_t tid = threadIdx.x;
     const uint64_t i = (uint64_t)blockIdx.x * B + tid;
     const bool pass = i < a.n && a.first_fail[i] == a.c;
-    const uint64_t mask = __ballot(pass);
-    if (lane == 0) s_cnt[w] = (uint32_t)__popcll(mask);
-    __syncthreads();
-    uint32_t before = 0, all = 0;
-#pragma unroll
-    for (uint32_t u = 0; u < B / 64; ++u) {
-        const uint32_t s = s_cnt[u];
-        if (u < w) before += s;
-        all += s;
-    }
+    uint32_t rank[1], all[1];
+    block_ranks<B, 1>({pass}, s_cnt, rank, all);
     const uint64_t base = block_base[blockIdx.x];
-    if (pass) a.match[base + before + (uint32_t)__popcll(mask & ((1ull << lane) - 1))] = i;
-    if (blockIdx.x == gridDim.x - 1 && tid == 0) *a.match_count = base + all;
+    if (pass) a.match[base + rank[0]] = i;
+    if (blockIdx.x == gridDim.x - 1 && tid == 0) *a.match_count = base + all[0];
 }
 
 }  // namespace
@@ -101,18 +88,9 @@ hipError_t launch_check_encoded(const CheckArgs& a, hipStream_t stream, bool* no
     const uint64_t blocks = (a.n + kCheckBlock - 1) / kCheckBlock;
     if (blocks > 0x7fffffffULL) return hipErrorInvalidValue;
     if (a.n == 0) return a.match ? hipMemsetAsync(a.match_count, 0, sizeof(uint64_t), stream) : hipSuccess;
-    uint64_t* counts = nullptr;  // [blocks] | the scan's block sums
-    if (a.match) {
-        hipMemPool_t pool = nullptr;
-        hipError_t e = scratch_pool(&pool);
-        if (e == hipSuccess)
-            e = hipMallocFromPoolAsync((void**)&counts, (blocks + scan_scratch_words(blocks)) * 8, pool, stream);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            *no_scratch = true;
-            return hipSuccess;
-        }
-    }
+    PoolScratch scratch;  // [blocks] | the scan's block sums
+    if (a.match && !scratch.acquire((blocks + scan_scratch_words(blocks)) * 8, stream, no_scratch)) return hipSuccess;
+    uint64_t* counts = static_cast<uint64_t*>(scratch.p);
     const size_t lds = check_lds_bytes(kCheckBlock, a.c) + (kCheckBlock / 64) * 4;
     if (rx && rx->count)
         hipLaunchKernelGGL(check_kernel<RegexArgs>, dim3((uint32_t)blocks), dim3(kCheckBlock),
@@ -127,10 +105,8 @@ hipError_t launch_check_encoded(const CheckArgs& a, hipStream_t stream, bool* no
                                (const uint64_t*)counts);
             e = hipGetLastError();
         }
-        const hipError_t f = hipFreeAsync(counts, stream);
-        if (e == hipSuccess) e = f;
     }
-    return e;
+    return scratch.release(e);
 }
 
 }  // namespace hdx

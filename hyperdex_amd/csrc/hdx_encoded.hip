@@ -27,21 +27,18 @@
 #include "hdx_loads.h"
 #include "hdx_region_lookup.h"
 #include "hdx_variants.h"
+#include "hdx_wave.h"
 
 namespace hdx {
 
-typedef uint32_t __attribute__((aligned(1))) u32_u;
-typedef uint64_t __attribute__((aligned(1))) u64_u;
-typedef uint16_t __attribute__((aligned(1))) u16_u;
-
 __device__ __forceinline__ uint32_t load_be32(const uint8_t* p) {
-    return __builtin_bswap32(*(const __attribute__((address_space(1))) u32_u*)p);
+    return __builtin_bswap32(*(gu32_ptr)p);
 }
 __device__ __forceinline__ uint64_t load_be64(const uint8_t* p) {
-    return __builtin_bswap64(*(const __attribute__((address_space(1))) u64_u*)p);
+    return __builtin_bswap64(*(gu64_ptr)p);
 }
 __device__ __forceinline__ uint32_t load_be16(const uint8_t* p) {
-    const uint16_t v = *(const __attribute__((address_space(1))) u16_u*)p;
+    const uint16_t v = *(gu16_ptr)p;
     return (uint32_t)(uint16_t)((v >> 8) | (v << 8));
 }
 
@@ -133,7 +130,7 @@ hash_encoded_kernel(const EncodedArgs a) {
     if (TOUCH) {
         const uint32_t touch = vlen >= 4 ? min(vlen - 3, 4096u) : 0u;
         for (uint32_t off = 0; off < touch; off += 128)
-            sink ^= *(const __attribute__((address_space(1))) u32_u*)(v + off);
+            sink ^= *(gu32_ptr)(v + off);
     }
 
     // phase 1: decode_value (datalayer_encodings.cc:168-217) into descriptors
@@ -156,7 +153,7 @@ hash_encoded_kernel(const EncodedArgs a) {
             for (uint32_t m = 0; m < kRun; ++m) {
                 const bool room = m < R && ok && vlen - pos >= 12 * (m + 1);
                 hd[m] = room ? load_be32(v + pos + 12 * m) : 0u;
-                bits[m] = room ? *(const __attribute__((address_space(1))) u64_u*)(v + pos + 12 * m + 4) : 0;
+                bits[m] = room ? *(gu64_ptr)(v + pos + 12 * m + 4) : 0;
             }
             bool spec = true;
 #pragma unroll
@@ -176,7 +173,7 @@ hash_encoded_kernel(const EncodedArgs a) {
                         } else {  // off the predicted positions: one prefix at a time
                             spec = false;
                             lm = load_be32(v + pos);
-                            b = lm == 8 && vlen - pos >= 12 ? *(const __attribute__((address_space(1))) u64_u*)(v + pos + 4)
+                            b = lm == 8 && vlen - pos >= 12 ? *(gu64_ptr)(v + pos + 4)
                                                             : 0;
                         }
                         pos += 4;
@@ -201,7 +198,7 @@ hash_encoded_kernel(const EncodedArgs a) {
                     // the 8 value bytes are read with the prefix when the value has room for them
                     const bool room = vlen - pos >= 12;
                     len = load_be32(v + pos);
-                    const uint64_t bits = room ? *(const __attribute__((address_space(1))) u64_u*)(v + pos + 4) : 0;
+                    const uint64_t bits = room ? *(gu64_ptr)(v + pos + 4) : 0;
                     pos += 4;
                     if (len > vlen - pos) ok = false;
                     else if (cj == CODE_ZERO) h = 0;                  // datatype_info.cc:169-180

@@ -6,7 +6,7 @@
 //
 //   plan  gather_plan_kernel: a lane per record stores its size (0 past the
 //         count and for an index >= n) and its key length; then scan_exclusive
-//         (hdx_index_entries.hip) over the cap + 1 sizes, the last one 0, so
+//         (hdx_scratch.hip) over the cap + 1 sizes, the last one 0, so
 //         rec_off[cap] is the total.
 //   fill  gather_fill_kernel, tile-owned: the output is cut into tiles of
 //         kGatherTileBytes from its 16-byte-aligned base, a wave per tile, so
@@ -26,9 +26,9 @@
 //             keys put two in a chunk, empty records any number): an
 //             unaligned 8- or 4-byte load lying wholly inside the key or
 //             value, or, for 1-3 bytes, the one or two aligned dwords that
-//             hold the bytes taken (each holds a byte of the object, so it
-//             lies in the object's pages).  No dword without a byte of the
-//             object is read.
+//             hold the bytes taken (tail_bytes, hdx_wave.h: each holds a
+//             byte of the object, so it lies in the object's pages).  No
+//             dword without a byte of the object is read.
 //         Whole chunks are stored as 16 aligned bytes; the chunks at the
 //         output's two ends, shared with the caller's memory, byte by byte,
 //         only the output's own bytes, never read (index_fill_kernel's rule).
@@ -41,19 +41,11 @@
 #include <stdint.h>
 
 #include "hdx_internal.h"
+#include "hdx_wave.h"
 
 namespace hdx {
 
 namespace {
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t __attribute__((aligned(1))) go_u32_u;
-typedef uint64_t __attribute__((aligned(1))) go_u64_u;
-typedef u32x4 __attribute__((aligned(1))) go_u32x4_u;
-typedef const __attribute__((address_space(1))) uint32_t* go_g32a_ptr;  // aligned
-typedef const __attribute__((address_space(1))) go_u32_u* go_g32_ptr;
-typedef const __attribute__((address_space(1))) go_u64_u* go_g64_ptr;
-typedef const __attribute__((address_space(1))) go_u32x4_u* go_g128_ptr;
 
 constexpr uint32_t kChunk = 16;                        // bytes a lane stores per step
 constexpr uint32_t kStepBytes = 64 * kChunk;           // a wave's step
@@ -86,20 +78,11 @@ __global__ void __launch_bounds__(256) gather_plan_kernel(const GatherObjectsArg
         a.rec_off[r] = size;
         if (a.rec_key_len) a.rec_key_len[r] = kl;
     }
-    if (a.status) {  // one atomic per wave
-        const bool any_bad = __any(bad);
-        if ((threadIdx.x & 63) == 0 && any_bad) atomicOr(a.status, 1u << 4 /* HDX_E_INVALID */);
-    }
+    wave_status_or(a.status, bad, kStatusInvalid);
     if (r == 0) a.rec_off[a.cap] = 0;  // the scan's last element: the total lands here
 }
 
 // ---- fill -----------------------------------------------------------------
-
-__device__ __forceinline__ void gather_wave_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // What a wave keeps in LDS of kWindow consecutive records from record r on:
 // ro[j] = rec_off[min(r + j, cap)], and of each record with bytes in the
@@ -133,7 +116,7 @@ __device__ __forceinline__ uint64_t first_record(const uint64_t* rec_off, uint64
 // other record size 0) and starts before tile_end.
 __device__ __forceinline__ void stage_window(GatherWindow& g, const GatherObjectsArgs& a, uint64_t r,
                                              uint64_t tile_end, uint32_t lane) {
-    gather_wave_fence();  // the previous window is done with
+    wave_fence();  // the previous window is done with
     const uint64_t j = r + lane;
     const uint64_t o0 = a.rec_off[std::min<uint64_t>(j, a.cap)];
     const uint64_t o1 = a.rec_off[std::min<uint64_t>(j + 1, a.cap)];
@@ -152,7 +135,7 @@ __device__ __forceinline__ void stage_window(GatherWindow& g, const GatherObject
         g.ksrc[lane] = ks;
         g.vsrc[lane] = vs;
     }
-    gather_wave_fence();
+    wave_fence();
 }
 
 // v into dword w of the chunk (no indexed register array)
@@ -189,26 +172,16 @@ __device__ __forceinline__ uint64_t chunk_bytes(const GatherWindow& g, uint64_t 
         const uint32_t b = (uint32_t)(p - cpos);  // the byte of the chunk p is
         const uint64_t room = std::min<uint64_t>(rem, lim - p);
         if (b == 0 && room >= kChunk) {
-            o = *(go_g128_ptr)src;
+            o = *(gu128_ptr)src;
             p += kChunk;
         } else if ((b & 3) == 0 && room >= 8) {  // b <= 8
-            const uint64_t v = *(go_g64_ptr)src;
+            const uint64_t v = *(gu64_ptr)src;
             put_dword(o, b >> 2, (uint32_t)v);
             put_dword(o, (b >> 2) + 1, (uint32_t)(v >> 32));
             p += 8;
         } else {  // up to the end of the chunk's dword
             const uint32_t take = (uint32_t)std::min<uint64_t>(room, 4 - (b & 3));
-            uint32_t got;
-            if (take == 4) {
-                got = *(go_g32_ptr)src;
-            } else {  // the aligned dwords that hold the bytes taken
-                const uint32_t sh = (uint32_t)(uintptr_t)src & 3;
-                const uint8_t* q = src - sh;
-                const uint32_t d0 = *(go_g32a_ptr)q;
-                const uint32_t d1 = sh + take > 4 ? *(go_g32a_ptr)(q + 4) : 0u;
-                got = __builtin_amdgcn_alignbyte(d1, d0, sh) & ((1u << (8 * take)) - 1);
-            }
-            put_dword(o, b >> 2, got << (8 * (b & 3)));
+            put_dword(o, b >> 2, tail_bytes(src, take) << (8 * (b & 3)));
             p += take;
         }
     }
@@ -220,7 +193,7 @@ __global__ void __launch_bounds__(256) gather_fill_kernel(const GatherObjectsArg
     const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const uint64_t total = a.rec_off[a.cap];
     if (total > a.out_bytes) {  // the caller's buffer is too small: nothing is written
-        if (blockIdx.x == 0 && threadIdx.x == 0 && a.status) atomicOr(a.status, 1u << 5 /* HDX_E_NOMEM */);
+        if (blockIdx.x == 0 && threadIdx.x == 0 && a.status) atomicOr(a.status, kStatusNoMem);
         return;
     }
     if (total == 0) return;
@@ -276,25 +249,12 @@ hipError_t launch_gather_objects_plan(const GatherObjectsArgs& a, hipStream_t st
     const uint64_t blocks = std::max<uint64_t>((a.cap + 255) / 256, 1);
     if (blocks > 0x7fffffffULL) return hipErrorInvalidValue;
     const uint64_t words = scan_scratch_words(N);
-    uint64_t* scratch = nullptr;
-    if (words) {
-        hipMemPool_t pool = nullptr;
-        hipError_t e = scratch_pool(&pool);
-        if (e == hipSuccess) e = hipMallocFromPoolAsync((void**)&scratch, words * 8, pool, stream);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            *no_scratch = true;
-            return hipSuccess;
-        }
-    }
+    PoolScratch sums;
+    if (words && !sums.acquire(words * 8, stream, no_scratch)) return hipSuccess;
     hipLaunchKernelGGL(gather_plan_kernel, dim3((uint32_t)blocks), dim3(256), 0, stream, a);
     hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = scan_exclusive(a.rec_off, N, scratch, stream);
-    if (scratch) {
-        const hipError_t f = hipFreeAsync(scratch, stream);
-        if (e == hipSuccess) e = f;
-    }
-    return e;
+    if (e == hipSuccess) e = scan_exclusive(a.rec_off, N, static_cast<uint64_t*>(sums.p), stream);
+    return sums.release(e);
 }
 
 hipError_t launch_gather_objects_fill(const GatherObjectsArgs& a, hipStream_t stream) {
@@ -314,7 +274,7 @@ __global__ void __launch_bounds__(256) gather_extents_plan_kernel(const GatherOb
                                                                    uint32_t* len, uint64_t* dst_off) {
     const uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     const bool fits = a.rec_off[a.cap] <= a.out_bytes;
-    if (r == 0 && !fits && a.status) atomicOr(a.status, 1u << 5 /* HDX_E_NOMEM */);
+    if (r == 0 && !fits && a.status) atomicOr(a.status, kStatusNoMem);
     if (r >= a.cap) return;
     const uint64_t at = a.rec_off[r], size = a.rec_off[r + 1] - at;
     uint32_t kl = 0, vl = 0;
@@ -344,25 +304,16 @@ hipError_t launch_gather_objects_by_extents(const GatherObjectsArgs& a, hipStrea
     *no_scratch = false;
     const uint64_t E = 2 * a.cap, blocks = std::max<uint64_t>((a.cap + 255) / 256, 1);
     if (blocks > 0x7fffffffULL) return hipErrorInvalidValue;
-    uint8_t* scratch = nullptr;
-    hipMemPool_t pool = nullptr;
-    hipError_t e = scratch_pool(&pool);
-    if (e == hipSuccess) e = hipMallocFromPoolAsync((void**)&scratch, std::max<uint64_t>(E, 1) * 20, pool, stream);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        *no_scratch = true;
-        return hipSuccess;
-    }
-    uint64_t* src_off = reinterpret_cast<uint64_t*>(scratch);
+    PoolScratch scratch;
+    if (!scratch.acquire(std::max<uint64_t>(E, 1) * 20, stream, no_scratch)) return hipSuccess;
+    uint64_t* src_off = static_cast<uint64_t*>(scratch.p);
     uint64_t* dst_off = src_off + E;
     uint32_t* len = reinterpret_cast<uint32_t*>(dst_off + E);
     hipLaunchKernelGGL(gather_extents_plan_kernel, dim3((uint32_t)blocks), dim3(256), 0, stream, a, src_off, len,
                        dst_off);
-    e = hipGetLastError();
-    if (e == hipSuccess)
-        e = launch_gather_extents(nullptr, src_off, len, dst_off, a.out, E, stream);
-    const hipError_t f = hipFreeAsync(scratch, stream);
-    return e == hipSuccess ? f : e;
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = launch_gather_extents(nullptr, src_off, len, dst_off, a.out, E, stream);
+    return scratch.release(e);
 }
 #endif
 

@@ -21,11 +21,10 @@
 
 #include "hdx_device_hash.h"
 #include "hdx_internal.h"
+#include "hdx_wave.h"
 
 namespace hdx {
 
-typedef uint64_t __attribute__((aligned(1))) u64_u;
-typedef const __attribute__((address_space(1))) u64_u* gu64_ptr;
 // FLOAT's 16-byte key goes out as one vector store that claims only the 8-byte
 // alignment include/hdxhash.h asks of `out` (a uint64_t array works)
 typedef u64x2 __attribute__((aligned(8))) u64x2_a8;

@@ -11,13 +11,8 @@
 //         descriptors of the indexed attributes in LDS, and the workgroup then
 //         stores attr_off, attr_len and the entry sizes of its objects
 //         coalesced.
-//   scan  the exclusive prefix sum of the n*m + 1 sizes (the last one is 0,
-//         so entry_off[n*m] is the total), reduce-then-scan over separate
-//         launches: index_scan_sums_kernel (one sum per kIndexScanBlock
-//         elements), the same scan over those sums (recursively: a further
-//         level per factor of kIndexScanBlock), index_scan_block_kernel (each
-//         workgroup scans its elements and adds its sum's prefix).  No kernel
-//         waits on another workgroup: the order is the stream's.
+//   scan  scan_exclusive (hdx_scratch.hip): the exclusive prefix sum of the
+//         n*m + 1 sizes (the last one is 0, so entry_off[n*m] is the total).
 //   fill  index_fill_kernel: a wave per group of up to 16 consecutive objects
 //         (at most 64 entries).  Object-major order makes the group's entries
 //         one contiguous span of the output, which the wave owns; it loads the
@@ -28,7 +23,8 @@
 //         waves (or the caller's memory) share are written byte by byte,
 //         only the span's own bytes, never read.  Source bytes are read as
 //         unaligned dwords / 8-byte values lying wholly inside a key or an
-//         attribute, or as the aligned dwords that hold the bytes taken.
+//         attribute, or as the aligned dwords that hold the bytes taken
+//         (tail_dwords, hdx_wave.h).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -41,11 +37,6 @@
 namespace hdx {
 
 namespace {
-
-typedef uint32_t __attribute__((aligned(1))) ie_u32_u;
-typedef uint64_t __attribute__((aligned(1))) ie_u64_u;
-typedef const __attribute__((address_space(1))) ie_u32_u* ie_gu32_ptr;
-typedef const __attribute__((address_space(1))) ie_u64_u* ie_gu64_ptr;
 
 constexpr uint32_t kRefused = 0xffffffffu;
 
@@ -95,13 +86,8 @@ __global__ void __launch_bounds__(256) index_plan_kernel(const IndexEntriesArgs 
         badsize = badsize && ok;
         s_key[tid] = (badenc || badsize) ? kRefused : enc_size(a.key_enc, kl);
     }
-    if (a.status) {  // one atomic per wave and bit
-        const bool any_enc = __any(badenc), any_size = __any(badsize);
-        if ((tid & 63) == 0) {
-            if (any_enc) atomicOr(a.status, 1u << 6 /* HDX_E_BADENC */);
-            if (any_size) atomicOr(a.status, 1u << 2 /* HDX_E_BADSIZE */);
-        }
-    }
+    wave_status_or(a.status, badenc, kStatusBadEnc);  // one atomic per wave and bit
+    wave_status_or(a.status, badsize, kStatusBadSize);
     __syncthreads();
     const uint64_t left = a.n - first;  // > 0: the grid covers n exactly
     const uint32_t cnt = (uint32_t)std::min<uint64_t>(B, left) * m;
@@ -125,107 +111,7 @@ __global__ void __launch_bounds__(256) index_plan_kernel(const IndexEntriesArgs 
     if (blockIdx.x == 0 && tid == 0) a.entry_off[a.n * m] = 0;  // the scan's last element: the total lands here
 }
 
-// ---- scan -----------------------------------------------------------------
-
-constexpr uint32_t kScanThreads = 256;
-constexpr uint32_t kScanItems = kIndexScanBlock / kScanThreads;
-static_assert(kScanItems * kScanThreads == kIndexScanBlock, "scan block");
-
-// exclusive prefix of x over the workgroup's threads; *total = the sum
-__device__ __forceinline__ uint64_t block_exclusive(uint64_t x, uint64_t* total) {
-    __shared__ uint64_t wave_sum[kScanThreads / 64];
-    const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    uint64_t incl = x;
-#pragma unroll
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-        const uint64_t y = (uint64_t)__shfl_up((unsigned long long)incl, d, 64);
-        if (lane >= d) incl += y;
-    }
-    if (lane == 63) wave_sum[w] = incl;
-    __syncthreads();
-    uint64_t before = 0, all = 0;
-#pragma unroll
-    for (uint32_t u = 0; u < kScanThreads / 64; ++u) {
-        const uint64_t s = wave_sum[u];
-        if (u < w) before += s;
-        all += s;
-    }
-    *total = all;
-    return before + incl - x;
-}
-
-__global__ void __launch_bounds__(kScanThreads) index_scan_sums_kernel(const uint64_t* data, uint64_t N,
-                                                                        uint64_t* sums) {
-    const uint64_t base = (uint64_t)blockIdx.x * kIndexScanBlock + (uint64_t)threadIdx.x * kScanItems;
-    uint64_t x = 0;
-#pragma unroll
-    for (uint32_t q = 0; q < kScanItems; ++q)
-        if (base + q < N) x += data[base + q];
-    uint64_t total;
-    (void)block_exclusive(x, &total);
-    if (threadIdx.x == 0) sums[blockIdx.x] = total;
-}
-
-// sums: this level's block sums already scanned (exclusive), or NULL for a
-// level of one workgroup
-__global__ void __launch_bounds__(kScanThreads) index_scan_block_kernel(uint64_t* data, uint64_t N,
-                                                                         const uint64_t* sums) {
-    const uint64_t base = (uint64_t)blockIdx.x * kIndexScanBlock + (uint64_t)threadIdx.x * kScanItems;
-    uint64_t v[kScanItems];
-    uint64_t x = 0;
-#pragma unroll
-    for (uint32_t q = 0; q < kScanItems; ++q) {
-        v[q] = base + q < N ? data[base + q] : 0;
-        x += v[q];
-    }
-    uint64_t total;
-    uint64_t run = block_exclusive(x, &total) + (sums ? sums[blockIdx.x] : 0);
-#pragma unroll
-    for (uint32_t q = 0; q < kScanItems; ++q) {
-        if (base + q < N) data[base + q] = run;
-        run += v[q];
-    }
-}
-
-}  // namespace
-
-hipError_t scan_exclusive(uint64_t* data, uint64_t N, uint64_t* scratch, hipStream_t stream) {
-    const uint64_t blocks = (N + kIndexScanBlock - 1) / kIndexScanBlock;
-    if (blocks > 0x7fffffffULL) return hipErrorInvalidValue;
-    if (blocks <= 1) {
-        hipLaunchKernelGGL(index_scan_block_kernel, dim3(1), dim3(kScanThreads), 0, stream, data, N,
-                           (const uint64_t*)nullptr);
-        return hipGetLastError();
-    }
-    hipLaunchKernelGGL(index_scan_sums_kernel, dim3((uint32_t)blocks), dim3(kScanThreads), 0, stream, data, N,
-                       scratch);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    if ((e = scan_exclusive(scratch, blocks, scratch + blocks, stream)) != hipSuccess) return e;
-    hipLaunchKernelGGL(index_scan_block_kernel, dim3((uint32_t)blocks), dim3(kScanThreads), 0, stream, data, N,
-                       (const uint64_t*)scratch);
-    return hipGetLastError();
-}
-
-// u64 words of block sums over every level of a scan of N elements
-uint64_t scan_scratch_words(uint64_t N) {
-    uint64_t words = 0;
-    while (N > kIndexScanBlock) {
-        N = (N + kIndexScanBlock - 1) / kIndexScanBlock;
-        words += N;
-    }
-    return words;
-}
-
-namespace {
-
 // ---- fill -----------------------------------------------------------------
-
-__device__ __forceinline__ void fill_wave_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // The bytes of one segment of an entry, from offset r on: `rem` of them.
 // src != NULL: raw bytes of a key or an attribute at src; else the immediate
@@ -239,18 +125,12 @@ struct Seg {
 
 // Up to four bytes of the segment from offset s.r on, in the low bytes of the
 // result (the bytes past `take` are unspecified: the caller masks them).
-// Raw bytes: one unaligned dword when all four are the segment's, else the one
-// or two aligned dwords that hold the bytes taken (they hold source bytes, so
-// they lie in the source's pages).
+// Raw bytes: by the load rule of hdx_wave.h (tail_bytes without its mask).
 __device__ __forceinline__ uint32_t seg_bytes(const Seg& s, uint32_t take) {
     if (s.src) {
         const uint8_t* p = s.src + s.r;
-        if (take == 4) return *(ie_gu32_ptr)p;
-        const uint32_t sh = (uint32_t)(uintptr_t)p & 3;
-        const uint8_t* q = p - sh;
-        const uint32_t d0 = *(const __attribute__((address_space(1))) uint32_t*)q;
-        const uint32_t d1 = sh + take > 4 ? *(const __attribute__((address_space(1))) uint32_t*)(q + 4) : 0u;
-        return __builtin_amdgcn_alignbyte(d1, d0, sh);
+        if (take == 4) return *(gu32_ptr)p;
+        return tail_dwords(p, take);
     }
     if (s.lds_prefix) {  // dwords of the prefix table (padded by one dword)
         const uint32_t* w = reinterpret_cast<const uint32_t*>(s.lds_prefix) + (s.r >> 2);
@@ -270,7 +150,7 @@ __device__ __forceinline__ void seg_encoded(Seg& s, uint32_t enc, const uint8_t*
         s.rem = len - r;
         return;
     }
-    const uint64_t bits = len == 8 ? *(ie_gu64_ptr)p : 0;  // the plan admits only 0 and 8
+    const uint64_t bits = len == 8 ? *(gu64_ptr)p : 0;  // the plan admits only 0 and 8
     if (enc == ENC_INT64) {
         s.lo = __builtin_bswap64(encode_int64(bits));
         s.rem = 8 - r;
@@ -313,7 +193,7 @@ __global__ void __launch_bounds__(256) index_fill_kernel(const IndexEntriesArgs 
     }
     __syncthreads();
     if (a.entry_off[a.n * m] > a.entries_bytes) {  // the caller's buffer is too small: nothing is written
-        if (blockIdx.x == 0 && threadIdx.x == 0 && a.status) atomicOr(a.status, 1u << 5 /* HDX_E_NOMEM */);
+        if (blockIdx.x == 0 && threadIdx.x == 0 && a.status) atomicOr(a.status, kStatusNoMem);
         return;
     }
     FillGroup& g = s_group[w];
@@ -323,7 +203,7 @@ __global__ void __launch_bounds__(256) index_fill_kernel(const IndexEntriesArgs 
     for (uint64_t gi = (uint64_t)blockIdx.x * 4 + w; gi < groups; gi += nwaves) {
         const uint64_t i0 = gi * G;
         const uint32_t objs = (uint32_t)std::min<uint64_t>(G, a.n - i0), E = objs * m;  // E <= 64
-        fill_wave_fence();  // the previous group's tables are done with
+        wave_fence();  // the previous group's tables are done with
         if (lane < E) {
             g.eo[lane] = a.entry_off[i0 * m + lane];
             g.aoff[lane] = a.attr_off[i0 * m + lane];
@@ -336,7 +216,7 @@ __global__ void __launch_bounds__(256) index_fill_kernel(const IndexEntriesArgs 
             g.klen[lane] = a.key_len[i0 + lane];
             g.voff[lane] = a.val_off[i0 + lane];
         }
-        fill_wave_fence();
+        wave_fence();
         const uint64_t s = g.eo[0], e = g.eo[E];
         if (s == e) continue;  // every object of the group is refused
         // the aligned dwords that hold bytes [dst + s, dst + e)
@@ -405,29 +285,16 @@ hipError_t launch_index_entries_plan(const IndexEntriesArgs& a, hipStream_t stre
     if (blocks > 0x7fffffffULL || (N + kIndexScanBlock - 1) / kIndexScanBlock > 0x7fffffffULL)
         return hipErrorInvalidValue;
     const uint64_t words = scan_scratch_words(N);
-    uint64_t* scratch = nullptr;
-    if (words) {
-        hipMemPool_t pool = nullptr;
-        hipError_t e = scratch_pool(&pool);
-        if (e == hipSuccess) e = hipMallocFromPoolAsync((void**)&scratch, words * 8, pool, stream);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            *no_scratch = true;
-            return hipSuccess;
-        }
-    }
+    PoolScratch sums;
+    if (words && !sums.acquire(words * 8, stream, no_scratch)) return hipSuccess;
     hipError_t e = hipSuccess;
     if (a.n) {
         const size_t lds = (size_t)B * a.m * 8 + (size_t)B * 4 + 2 * HDX_MAX_INDICES;
         hipLaunchKernelGGL(index_plan_kernel, dim3((uint32_t)blocks), dim3(B), lds, stream, a);
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = scan_exclusive(a.entry_off, N, scratch, stream);
-    if (scratch) {
-        const hipError_t f = hipFreeAsync(scratch, stream);
-        if (e == hipSuccess) e = f;
-    }
-    return e;
+    if (e == hipSuccess) e = scan_exclusive(a.entry_off, N, static_cast<uint64_t*>(sums.p), stream);
+    return sums.release(e);
 }
 
 hipError_t launch_index_entries_fill(const IndexEntriesArgs& a, hipStream_t stream) {

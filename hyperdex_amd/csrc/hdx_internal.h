@@ -127,7 +127,6 @@ hipError_t launch_lookup_region(const RegionArgs& a, hipStream_t stream);
 using RegionHashFn = std::function<hipError_t(uint64_t first, uint64_t count, uint64_t* coords)>;
 constexpr uint64_t kRegionChunkBytes = 2ull << 30;
 constexpr uint64_t kRegionLookupMinObjects = 1ull << 20;
-void trim_scratch_pools();  // hdx_regions.hip: release the scratch pools' cached memory (scratch_pool, below)
 bool regions_by_lookup_pays(uint64_t n);
 uint64_t regions_chunk_objects(uint64_t n, uint32_t A);
 hipError_t regions_by_lookup(uint64_t n, uint32_t A, const SweepTable* t, uint32_t T, uint64_t* coords,
@@ -209,11 +208,32 @@ struct IndexArgs {
 
 hipError_t launch_index_encode(const IndexArgs& a, hipStream_t stream);
 
+// Stream-ordered scratch and the prefix sum (hdx_scratch.hip).
+// A buffer from the library's per-device memory pool (the regions' coordinate
+// chunks, the scan's block sums, the stored-object stages' arrays), on the
+// calling thread's current device.  acquire before the first launch: on
+// failure HIP's last error is cleared, *no_scratch is set and false comes back
+// — nothing may be launched.  release(e): frees it behind the work on the
+// stream (nothing to free: no call) and returns e, or the free's error where e
+// is hipSuccess.
+struct PoolScratch {
+    void* p = nullptr;
+    hipStream_t stream = nullptr;
+    bool acquire(uint64_t bytes, hipStream_t s, bool* no_scratch);
+    hipError_t release(hipError_t e);
+};
+void trim_scratch_pools();  // release the pools' cached memory
+// The exclusive prefix sum of data[0..N) in place, reduce-then-scan over
+// separate launches; scratch holds scan_scratch_words(N) u64 of block sums
+// (none up to kIndexScanBlock).
+constexpr uint32_t kIndexScanBlock = 1024;  // elements per workgroup of the prefix sum
+hipError_t scan_exclusive(uint64_t* data, uint64_t N, uint64_t* scratch, hipStream_t stream);
+uint64_t scan_scratch_words(uint64_t N);
+
 // Secondary-index entries of stored objects (hdx_index_entries.hip): m
 // indices over n stored objects, entry e = i*m + k.  enc[] / key_enc hold the
 // index encoder of each indexed attribute and of the key (ENC_*,
 // hdx_host_common.h).
-constexpr uint32_t kIndexScanBlock = 1024;  // elements per workgroup of the entry-size prefix sum
 constexpr uint32_t kIndexPrefixStride = 24; // >= HDX_INDEX_PREFIX_MAX
 struct IndexEntriesArgs {
     const uint8_t* keys;      // fill only
@@ -236,17 +256,12 @@ struct IndexEntriesArgs {
     uint8_t plen[HDX_MAX_INDICES];
     uint8_t prefix[HDX_MAX_INDICES * kIndexPrefixStride];
 };
-// The walk (a lane per object), then the exclusive prefix sum of the entry
-// sizes over n*m + 1 elements, reduce-then-scan in separate launches.  Its
-// block sums come from the library's stream-ordered pool (scratch_pool); if
-// that allocation fails nothing is launched and *no_scratch is set.
+// The walk (a lane per object), then scan_exclusive over the n*m + 1 entry
+// sizes.  Its block sums come from the library's stream-ordered pool
+// (PoolScratch); if that allocation fails nothing is launched and *no_scratch
+// is set.
 hipError_t launch_index_entries_plan(const IndexEntriesArgs& a, hipStream_t stream, bool* no_scratch);
 hipError_t launch_index_entries_fill(const IndexEntriesArgs& a, hipStream_t stream);
-// The reduce-then-scan itself (hdx_index_entries.hip): the exclusive prefix
-// sum of data[0..N) in place, over separate launches; scratch holds
-// scan_scratch_words(N) u64 of block sums (none up to kIndexScanBlock).
-hipError_t scan_exclusive(uint64_t* data, uint64_t N, uint64_t* scratch, hipStream_t stream);
-uint64_t scan_scratch_words(uint64_t N);
 
 // The objects behind a list of indices, packed (hdx_gather_objects.hip):
 // record r = [key of idx[r] if KEYS][value of idx[r] if VALUES] at out +
@@ -270,7 +285,7 @@ struct GatherObjectsArgs {
     uint32_t what;            // HDX_GATHER_KEYS | HDX_GATHER_VALUES
 };
 // A lane per record stores its size, then scan_exclusive over cap + 1
-// elements; block sums from scratch_pool, *no_scratch as above.
+// elements; block sums from the pool, *no_scratch as above.
 hipError_t launch_gather_objects_plan(const GatherObjectsArgs& a, hipStream_t stream, bool* no_scratch);
 // Tile-owned: a wave per kGatherTileBytes of the output.
 hipError_t launch_gather_objects_fill(const GatherObjectsArgs& a, hipStream_t stream);
@@ -334,10 +349,6 @@ uint64_t sorted_scratch_bytes(uint64_t n);
 hipError_t launch_sorted_search(const SortedArgs& a, hipStream_t stream, bool* no_scratch,
                                 const RegexArgs* rx = nullptr);
 static_assert(sizeof(SortedArgs) + sizeof(RegexArgs) + 64 <= 3072, "kernel arguments: well under the 4 KiB limit");
-// hdx_regions.hip: the library's per-device memory pool for stream-ordered
-// scratch (the regions' coordinate chunks and this scan's block sums), on the
-// calling thread's current device.
-hipError_t scratch_pool(hipMemPool_t* out);
 
 // Search pruning (hdx_index.hip) over one subspace's region table: m ranges
 // that name a subspace attribute, in the order lookup_search visits them.

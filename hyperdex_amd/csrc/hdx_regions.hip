@@ -13,7 +13,6 @@
 #include <stdint.h>
 
 #include <algorithm>
-#include <mutex>
 
 #include "hdx_internal.h"
 #include "hdx_region_lookup.h"
@@ -101,82 +100,37 @@ uint64_t regions_chunk_objects(uint64_t n, uint32_t A) {
     return std::min<uint64_t>(n, std::max<uint64_t>(1, bytes / (8ull * A)));
 }
 
-// Stream-ordered scratch of the library — the regions' coordinate chunks
-// (below) and the block sums of the index entries' prefix sum
-// (hdx_index_entries.hip) — comes from a memory pool of the library's own per
-// device that keeps up to one region chunk cached between calls (the device's
-// default pool returns freed memory at every synchronisation, so each call
-// would map its scratch afresh); the pools are trimmed at hdx_shutdown.
-static std::mutex g_pool_mu;
-static hipMemPool_t g_pool[64];
-
-hipError_t scratch_pool(hipMemPool_t* out) {
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    std::lock_guard<std::mutex> lk(g_pool_mu);
-    if (!g_pool[dev]) {
-        hipMemPoolProps props{};
-        props.allocType = hipMemAllocationTypePinned;
-        props.location.type = hipMemLocationTypeDevice;
-        props.location.id = dev;
-        if ((e = hipMemPoolCreate(&g_pool[dev], &props)) != hipSuccess) {
-            g_pool[dev] = nullptr;
-            return e;
-        }
-        uint64_t keep = kRegionChunkBytes;
-        (void)hipMemPoolSetAttribute(g_pool[dev], hipMemPoolAttrReleaseThreshold, &keep);
-    }
-    *out = g_pool[dev];
-    return hipSuccess;
-}
-
-void trim_scratch_pools() {
-    std::lock_guard<std::mutex> lk(g_pool_mu);
-    for (hipMemPool_t p : g_pool)
-        if (p) (void)hipMemPoolTrimTo(p, 0);
-}
-
+// The coordinate chunks are scratch from the library's pool (PoolScratch,
+// hdx_scratch.hip).
 hipError_t regions_by_lookup(uint64_t n, uint32_t A, const SweepTable* t, uint32_t T, uint64_t* coords,
                              const RegionHashFn& hash, hipStream_t stream, bool* no_scratch) {
     *no_scratch = false;
     if (n == 0) return hipSuccess;
     const uint64_t chunk = coords ? n : regions_chunk_objects(n, A);
-    uint64_t* scratch = nullptr;
-    hipError_t e = hipSuccess;
+    PoolScratch scratch;
     if (!coords) {
-        hipMemPool_t pool = nullptr;
-        e = scratch_pool(&pool);
-        if (e == hipSuccess) e = hipMallocFromPoolAsync((void**)&scratch, chunk * A * 8, pool, stream);
+        // on failure nothing is launched yet: the caller runs its fused form,
+        // which needs no scratch (no new out-of-memory failure)
+        bool have = scratch.acquire(chunk * A * 8, stream, no_scratch);
 #if HDX_DEBUG_BUILD
-        if (e == hipSuccess && hash_variant() == 247) {  // tests: the allocation "fails"
-            (void)hipFreeAsync(scratch, stream);
-            scratch = nullptr;
-            e = hipErrorOutOfMemory;
+        if (have && hash_variant() == 247) {  // tests: the allocation "fails"
+            (void)scratch.release(hipSuccess);
+            *no_scratch = true;
+            have = false;
         }
 #endif
-        if (e != hipSuccess) {
-            // nothing launched yet: the caller runs its fused form, which
-            // needs no scratch (no new out-of-memory failure)
-            (void)hipGetLastError();
-            *no_scratch = true;
-            return hipSuccess;
-        }
+        if (!have) return hipSuccess;
     }
+    hipError_t e = hipSuccess;
     for (uint64_t first = 0; first < n && e == hipSuccess; first += chunk) {
         const uint64_t count = std::min(chunk, n - first);
-        uint64_t* c = coords ? coords + first * A : scratch;
+        uint64_t* c = coords ? coords + first * A : static_cast<uint64_t*>(scratch.p);
         if ((e = hash(first, count, c)) != hipSuccess) break;
         for (uint32_t k = 0; k < T && e == hipSuccess; ++k) {
             e = launch_lookup_region(RegionArgs{t[k], c, t[k].out + first, count, A}, stream);
         }
     }
-    if (scratch) {
-        const hipError_t f = hipFreeAsync(scratch, stream);
-        if (e == hipSuccess) e = f;
-    }
-    return e;
+    return scratch.release(e);
 }
 
 // One lane per (table, object): small batches from the daemon shim, where a

@@ -120,16 +120,14 @@ __global__ void __launch_bounds__(kCheckBlock) sorted_rank_kernel(const SortedAr
                 in = false;
                 badsize = true;
             } else {
-                const uint64_t bits = slen ? *(ck_gu64_ptr)p : 0;  // an empty value is 0 / 0.0
+                const uint64_t bits = slen ? *(gu64_ptr)p : 0;  // an empty value is 0 / 0.0
                 r = a.kind == SORT_INT64 ? bits ^ 0x8000000000000000ull : rank_float(bits);
             }
         }
         rank[i] = r;
         member[i] = in ? 1 : 0;
     }
-    const uint32_t bits = (__any(badenc) ? 1u << 6 /* HDX_E_BADENC */ : 0) |
-                          (__any(badsize) ? 1u << 2 /* HDX_E_BADSIZE */ : 0);
-    if (ck.status && bits && (tid & 63) == 0) atomicOr(ck.status, bits);
+    wave_status_or(ck.status, (__any(badenc) ? kStatusBadEnc : 0) | (__any(badsize) ? kStatusBadSize : 0));
 }
 
 // Pass p counts the members that agree with state->prefix above bit 64 - 8p
@@ -193,56 +191,31 @@ __global__ void __launch_bounds__(kBins) sorted_pick_kernel(const uint64_t* bins
     state->need = need - before;
 }
 
-// before / equal: member i's key lies strictly before the threshold / on it.
+// flag[kBefore] / flag[kEqual]: member i's key lies strictly before the
+// threshold / on it.  Ranked as two flags behind one barrier (block_ranks).
+enum : uint32_t { kBefore = 0, kEqual = 1 };
 __device__ __forceinline__ void candidate_flags(const uint64_t* rank, const uint8_t* member, uint64_t n, uint64_t i,
-                                                uint64_t flip, const SortState* state, bool* before, bool* equal) {
-    *before = *equal = false;
+                                                uint64_t flip, const SortState* state, bool (&flag)[2]) {
+    flag[kBefore] = flag[kEqual] = false;
     if (i < n && state->kept != 0 && member[i]) {
         const uint64_t k = rank[i] ^ flip, T = state->prefix;
-        *before = k < T;
-        *equal = k == T;
+        flag[kBefore] = k < T;
+        flag[kEqual] = k == T;
     }
-}
-
-// The ranks of this lane's two flags inside the workgroup, and the workgroup's totals.
-__device__ __forceinline__ void block_ranks(bool before, bool equal, uint32_t* rb, uint32_t* re, uint32_t* allb,
-                                            uint32_t* alle) {
-    __shared__ uint32_t s_b[kCheckBlock / 64], s_e[kCheckBlock / 64];
-    const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const uint64_t mb = __ballot(before), me = __ballot(equal);
-    if (lane == 0) {
-        s_b[w] = (uint32_t)__popcll(mb);
-        s_e[w] = (uint32_t)__popcll(me);
-    }
-    __syncthreads();
-    uint32_t bb = 0, be = 0, ab = 0, ae = 0;
-#pragma unroll
-    for (uint32_t u = 0; u < kCheckBlock / 64; ++u) {
-        if (u < w) {
-            bb += s_b[u];
-            be += s_e[u];
-        }
-        ab += s_b[u];
-        ae += s_e[u];
-    }
-    const uint64_t below = (1ull << lane) - 1;
-    *rb = bb + (uint32_t)__popcll(mb & below);
-    *re = be + (uint32_t)__popcll(me & below);
-    *allb = ab;
-    *alle = ae;
 }
 
 // counts[b] = workgroup b's keys before the threshold, counts[blocks + b] = its keys on it.
 __global__ void __launch_bounds__(kCheckBlock) sorted_count_kernel(const uint64_t* rank, const uint8_t* member,
                                                                    uint64_t n, uint64_t flip, const SortState* state,
                                                                    uint64_t* counts) {
-    bool before, equal;
-    candidate_flags(rank, member, n, (uint64_t)blockIdx.x * kCheckBlock + threadIdx.x, flip, state, &before, &equal);
-    uint32_t rb, re, ab, ae;
-    block_ranks(before, equal, &rb, &re, &ab, &ae);
+    __shared__ uint32_t s_cnt[2 * kCheckBlock / 64];
+    bool flag[2];
+    candidate_flags(rank, member, n, (uint64_t)blockIdx.x * kCheckBlock + threadIdx.x, flip, state, flag);
+    uint32_t r[2], all[2];
+    block_ranks<kCheckBlock, 2>(flag, s_cnt, r, all);
     if (threadIdx.x == 0) {
-        counts[blockIdx.x] = ab;
-        counts[gridDim.x + blockIdx.x] = ae;
+        counts[blockIdx.x] = all[kBefore];
+        counts[gridDim.x + blockIdx.x] = all[kEqual];
     }
 }
 
@@ -253,16 +226,18 @@ __global__ void __launch_bounds__(kCheckBlock) sorted_compact_kernel(const uint6
                                                                      SortState* state, const uint64_t* base,
                                                                      uint64_t* cand) {
     const uint64_t i = (uint64_t)blockIdx.x * kCheckBlock + threadIdx.x;
-    bool before, equal;
-    candidate_flags(rank, member, n, i, flip, state, &before, &equal);
-    uint32_t rb, re, ab, ae;
-    block_ranks(before, equal, &rb, &re, &ab, &ae);
+    __shared__ uint32_t s_cnt[2 * kCheckBlock / 64];
+    bool flag[2];
+    candidate_flags(rank, member, n, i, flip, state, flag);
+    uint32_t r[2], all[2];
+    block_ranks<kCheckBlock, 2>(flag, s_cnt, r, all);
     const uint64_t take = all_equal ? ~0ull : state->need;  // of the equal keys, in index order
     const uint64_t b0 = base[blockIdx.x], e0 = base[gridDim.x + blockIdx.x] - base[gridDim.x];
-    const uint64_t eq_before = e0 + re;
+    const uint64_t eq_before = e0 + r[kEqual];
     // positions: every candidate with a smaller index comes first; at most n in all
-    if (before || (equal && eq_before < take)) cand[b0 + rb + std::min(eq_before, take)] = i;
-    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) state->ncand = b0 + ab + std::min(e0 + ae, take);
+    if (flag[kBefore] || (flag[kEqual] && eq_before < take)) cand[b0 + r[kBefore] + std::min(eq_before, take)] = i;
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0)
+        state->ncand = b0 + all[kBefore] + std::min(e0 + all[kEqual], take);
 }
 
 // ---- finish ------------------------------------------------------------------
@@ -389,15 +364,9 @@ hipError_t launch_sorted_search(const SortedArgs& a, hipStream_t stream, bool* n
     const uint64_t blocks = (n + kCheckBlock - 1) / kCheckBlock;
     if (blocks > 0x3fffffffULL || a.limit > HDX_SORT_LIMIT_MAX) return hipErrorInvalidValue;
     if (n == 0) return hipMemsetAsync(a.top_count, 0, sizeof(uint64_t), stream);
-    hipMemPool_t pool = nullptr;
-    uint64_t* base = nullptr;
-    hipError_t e = scratch_pool(&pool);
-    if (e == hipSuccess) e = hipMallocFromPoolAsync((void**)&base, sorted_scratch_bytes(n), pool, stream);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        *no_scratch = true;
-        return hipSuccess;
-    }
+    PoolScratch scratch;
+    if (!scratch.acquire(sorted_scratch_bytes(n), stream, no_scratch)) return hipSuccess;
+    uint64_t* base = static_cast<uint64_t*>(scratch.p);
     SortScratch s;
     s.bins = base;
     s.state = reinterpret_cast<SortState*>(base + kPasses * kBins);
@@ -407,7 +376,7 @@ hipError_t launch_sorted_search(const SortedArgs& a, hipStream_t stream, bool* n
     s.member = reinterpret_cast<uint8_t*>(s.counts + 2 * blocks + scan_scratch_words(2 * blocks));
     const uint64_t flip = a.keep == HDX_KEEP_LARGEST ? ~0ull : 0;
     const uint32_t grid = (uint32_t)blocks, hist_grid = (uint32_t)std::min<uint64_t>(blocks, kHistBlocks);
-    e = hipMemsetAsync(base, 0, kHeadWords * 8, stream);
+    hipError_t e = hipMemsetAsync(base, 0, kHeadWords * 8, stream);
     if (e == hipSuccess) {
         const size_t lds = check_lds_bytes(kCheckBlock, a.ck.c);
         if (rx && rx->count)
@@ -438,8 +407,7 @@ hipError_t launch_sorted_search(const SortedArgs& a, hipStream_t stream, bool* n
                            (const uint64_t*)s.rank, (const uint64_t*)s.cand, (const SortState*)s.state, flip);
         e = hipGetLastError();
     }
-    const hipError_t f = hipFreeAsync(base, stream);
-    return e == hipSuccess ? f : e;
+    return scratch.release(e);
 }
 
 }  // namespace hdx

@@ -11,10 +11,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-namespace hdx {
+#include "hdx_wave.h"
 
-typedef uint32_t __attribute__((aligned(1))) walk_u32_u;
-typedef const __attribute__((address_space(1))) walk_u32_u* walk_gu32_ptr;
+namespace hdx {
 
 // Calls on_attr(j, pos, L) for attribute j = 1 .. A-1 in order: L bytes at
 // v + pos, lying inside the value.  Returns false where the value is refused
@@ -23,11 +22,11 @@ typedef const __attribute__((address_space(1))) walk_u32_u* walk_gu32_ptr;
 template <typename F>
 __device__ __forceinline__ bool value_walk(const uint8_t* v, uint32_t vlen, uint32_t A, F&& on_attr) {
     if (vlen < 10) return false;
-    if ((__builtin_bswap32(*(walk_gu32_ptr)(v + 6)) & 0xffffu) != A - 1) return false;  // the u16 at bytes 8..9
+    if ((__builtin_bswap32(*(gu32_ptr)(v + 6)) & 0xffffu) != A - 1) return false;  // the u16 at bytes 8..9
     uint32_t pos = 10;  // pos <= vlen throughout
     for (uint32_t j = 1; j < A; ++j) {
         if (vlen - pos < 4) return false;
-        const uint32_t L = __builtin_bswap32(*(walk_gu32_ptr)(v + pos));
+        const uint32_t L = __builtin_bswap32(*(gu32_ptr)(v + pos));
         pos += 4;
         if (L > vlen - pos) return false;
         on_attr(j, pos, L);
@@ -41,7 +40,7 @@ __device__ __forceinline__ bool value_walk(const uint8_t* v, uint32_t vlen, uint
 __device__ __forceinline__ void value_attr(const uint8_t* v, uint32_t attr, uint32_t* pos_out, uint32_t* len_out) {
     uint32_t pos = 10, L;
     for (uint32_t j = 1;; ++j) {
-        L = __builtin_bswap32(*(walk_gu32_ptr)(v + pos));
+        L = __builtin_bswap32(*(gu32_ptr)(v + pos));
         pos += 4;
         if (j == attr) break;
         pos += L;

@@ -10,17 +10,11 @@
 #include "hdx_internal.h"
 #include "hdx_lds_hash.h"
 #include "hdx_loads.h"
+#include "hdx_wave.h"
 
 namespace hdx {
 
 typedef __attribute__((address_space(3))) void* lds_void_t;
-
-// the wave's LDS accesses ordered (the class sort's phases, a window's reuse)
-__device__ __forceinline__ void wave_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // One attribute from global memory, any class (hash_blk on the A4 pieces).
 __device__ __forceinline__ uint64_t hash_one(uint32_t code, const uint8_t* p, uint32_t n, bool& bad) {
@@ -43,6 +37,5 @@ __device__ __forceinline__ uint64_t be64_at(const uint8_t* p) {
 }
 
 constexpr uint64_t kWideZero = ~0ull;  // a coordinate of 0 (the object does not decode)
-typedef uint32_t __attribute__((aligned(1))) u32_unaligned;
 
 }  // namespace hdx

@@ -126,7 +126,7 @@ __global__ void __launch_bounds__(256) sweep_wide_walk_kernel(const EncodedArgs 
                         ok = false;
                     } else {
                         const uint32_t L =
-                            __builtin_bswap32(*(const __attribute__((address_space(1))) u32_unaligned*)(v + pos));
+                            __builtin_bswap32(*(gu32_ptr)(v + pos));
                         pos += 4;
                         if (L > vlen - pos) {
                             ok = false;

@@ -86,7 +86,7 @@ __global__ void __launch_bounds__(64) sweep_wide_stream_kernel(const EncodedArgs
     auto ring_be32 = [&](uint64_t t) {
         const uint32_t r = (uint32_t)(t & (2 * CH - 1));
         return __builtin_amdgcn_readfirstlane(
-            __builtin_bswap32(*(const __attribute__((address_space(3))) u32_unaligned*)(
+            __builtin_bswap32(*(const __attribute__((address_space(3))) u32_u*)(
                 (const __attribute__((address_space(3))) uint8_t*)(lds_void_t)ring + r)));
     };
     if (nch) load(0);
@@ -167,7 +167,7 @@ __global__ void __launch_bounds__(256) sweep_wide_fused_kernel(const EncodedArgs
     }
     uint32_t pos = 10;  // the next prefix's offset; pos <= vlen while ok
     uint32_t Lnext = ok && A > 1 && vlen - pos >= 4
-                         ? __builtin_bswap32(*(const __attribute__((address_space(1))) u32_unaligned*)(v + pos))
+                         ? __builtin_bswap32(*(gu32_ptr)(v + pos))
                          : 0u;
     uint64_t buf[16];
     for (uint32_t j0 = 0; j0 < A; j0 += 16) {
@@ -186,7 +186,7 @@ __global__ void __launch_bounds__(256) sweep_wide_fused_kernel(const EncodedArgs
                 if (ok && L > vlen - at) ok = false;
                 const uint32_t np = ok ? at + L : pos;
                 Lnext = ok && j + 1 < A && vlen - np >= 4
-                            ? __builtin_bswap32(*(const __attribute__((address_space(1))) u32_unaligned*)(v + np))
+                            ? __builtin_bswap32(*(gu32_ptr)(v + np))
                             : 0u;
                 h = hash_one(ok ? (uint32_t)a.codes_dev[j] : (uint32_t)CODE_ZERO, v + at, ok ? L : 0u, bad);
                 pos = np;

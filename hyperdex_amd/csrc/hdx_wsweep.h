@@ -41,14 +41,12 @@
 #include "hdx_lds_hash.h"
 #include "hdx_region_lookup.h"
 #include "hdx_regroup.h"
+#include "hdx_wave.h"
 
 namespace hdx {
 namespace {
 
 typedef __attribute__((address_space(3))) void* lds_void_t;
-typedef uint32_t __attribute__((aligned(1))) u32_u;
-typedef uint64_t __attribute__((aligned(1))) u64_u;
-typedef uint16_t __attribute__((aligned(1))) u16_u;
 
 constexpr uint32_t kZero = 0xffffffffu;   // descriptor offset of a slot hashed as 0
 constexpr uint32_t kGlobal = 0x80000000u; // descriptor length bit: hashed from global memory
@@ -61,21 +59,16 @@ __device__ __forceinline__ uint64_t rl64(uint64_t v, int l) {
 __device__ __forceinline__ uint64_t sh64(uint64_t v, int l) {
     return pack64((uint32_t)__shfl((int)(uint32_t)v, l, 64), (uint32_t)__shfl((int)(uint32_t)(v >> 32), l, 64));
 }
-__device__ __forceinline__ void wave_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // big-endian fields at byte p of global memory / at byte offset o of the window
 __device__ __forceinline__ uint32_t g_be32(const uint8_t* p) {
-    return __builtin_bswap32(*(const __attribute__((address_space(1))) u32_u*)p);
+    return __builtin_bswap32(*(gu32_ptr)p);
 }
 __device__ __forceinline__ uint64_t g_be64(const uint8_t* p) {
-    return __builtin_bswap64(*(const __attribute__((address_space(1))) u64_u*)p);
+    return __builtin_bswap64(*(gu64_ptr)p);
 }
 __device__ __forceinline__ uint32_t g_be16(const uint8_t* p) {
-    const uint16_t v = *(const __attribute__((address_space(1))) u16_u*)p;
+    const uint16_t v = *(gu16_ptr)p;
     return (uint32_t)(uint16_t)((v >> 8) | (v << 8));
 }
 // The walk's big-endian reads at any byte offset: one misaligned ds_read_b32
