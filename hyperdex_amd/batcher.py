@@ -8,9 +8,8 @@ thread and coalesces the rest into device batches.  ctypes releases the GIL for 
 import ctypes
 from typing import List, Optional, Sequence, Tuple
 
-import numpy as np
-
 from ._lib import check, lib
+from ._tensors import types_array
 from .regions import RegionTable
 
 
@@ -38,7 +37,7 @@ class Batcher:
                  max_objects: int = 0, max_delay_us: int = 0, max_bytes: int = 0,
                  slots: int = 0, device: int = -1, stage_device: bool = False,
                  device_only: bool = False, host_max_bytes: int = 0):
-        self.types = np.ascontiguousarray(np.asarray(types, np.uint32))
+        self.types = types_array(types)
         self.A = len(self.types)
         self._tables = list(tables)  # keep the handles alive
         self._handles = (ctypes.c_void_p * max(len(tables), 1))(*[t.handle.value for t in tables])

@@ -12,9 +12,8 @@ check_encoded   a batch of stored objects on the GPU (hdx_check_encoded_device):
 import ctypes
 from typing import Sequence
 
-import numpy as np
-
 from ._lib import check, lib
+from ._tensors import check_stored, opt_ptr, ptrs, read_back, torch_stream, types_array
 
 HDX_MAX_CHECKS = 16
 HDX_CHECK_BYTES_MAX = 1024
@@ -55,7 +54,7 @@ def check_block_objects() -> int:
 def passes_checks(types, key: bytes, values: Sequence[bytes], checks: Sequence[AttributeCheck]) -> int:
     """passes_attribute_checks(schema, checks, key, value) for one object:
     the index of the first failing check, len(checks) when all pass."""
-    t = np.ascontiguousarray(np.asarray(types, dtype=np.uint32))
+    t = types_array(types)
     m = len(values)
     ptrs = (ctypes.c_char_p * max(m, 1))(*[bytes(v) for v in values])
     lens = (ctypes.c_size_t * max(m, 1))(*[len(v) for v in values])
@@ -73,7 +72,7 @@ def check_encoded(types, keys, key_off, key_len, vals, val_off, val_len, checks:
     (HDX_CHECK_BADENC) for a value that does not decode (status: HDX_E_BADENC's
     bit).  match: the indices with first_fail == len(checks), ascending; with
     want_match the count is read back on `stream`, which is then waited for."""
-    t = np.ascontiguousarray(np.asarray(types, dtype=np.uint32))
+    t = types_array(types)
     arr = _checks(checks)
 
     def call(ptrs, n, first_fail, match, count, status_ptr, stream_ptr):
@@ -87,31 +86,17 @@ def _check_encoded(call, keys, key_off, key_len, vals, val_off, val_len, want_ma
     count, status, stream) -> hdx_status."""
     import torch
 
-    from .index import _torch_stream
-
-    n = val_off.numel()
-    dev = val_off.device
-    for x in (keys, key_off, key_len, vals, val_off, val_len):
-        assert x.is_cuda and x.is_contiguous()
-    assert val_len.numel() == n and key_len.numel() == n and key_off.numel() == n
-    s = _torch_stream(stream, dev)
+    n, dev = check_stored(keys, key_off, key_len, vals, val_off, val_len)
+    s = torch_stream(stream, dev)
     with torch.cuda.stream(s):
         first_fail = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
         match = torch.empty(max(n, 1), dtype=torch.int64, device=dev) if want_match else None
         count = torch.empty(1, dtype=torch.int64, device=dev) if want_match else None
-    # tensors without elements have no address: first_fail stands in for them; nothing reads it when n == 0
-    keys, key_off, key_len, vals, val_off, val_len = [x if x.numel() else first_fail
-                                                      for x in (keys, key_off, key_len, vals, val_off, val_len)]
-    check(call([x.data_ptr() for x in (keys, key_off, key_len, vals, val_off, val_len)], n, first_fail.data_ptr(),
-               match.data_ptr() if want_match else None, count.data_ptr() if want_match else None,
-               status.data_ptr() if status is not None else None, s.cuda_stream))
+    check(call(ptrs((keys, key_off, key_len, vals, val_off, val_len), first_fail), n, first_fail.data_ptr(),
+               opt_ptr(match), opt_ptr(count), opt_ptr(status), s.cuda_stream))
     if not want_match:
         return first_fail[:n], None
-    with torch.cuda.stream(s):
-        host = torch.empty(1, dtype=torch.int64, pin_memory=True)
-        host.copy_(count, non_blocking=True)
-        s.synchronize()
-    return first_fail[:n], match[:int(host.item())]
+    return first_fail[:n], match[:read_back(count, s)]
 
 
 HDX_REGEX_ITEMS_MAX = 63
@@ -134,7 +119,7 @@ class CompiledChecks:
 
     def __init__(self, types, checks: Sequence[AttributeCheck]):
         self._h = None
-        t = np.ascontiguousarray(np.asarray(types, dtype=np.uint32))
+        t = types_array(types)
         h = ctypes.c_void_p(None)
         check(lib().hdx_checks_compile(t.ctypes.data, len(t), _checks(checks), len(checks), ctypes.byref(h)))
         self._h = h
@@ -180,7 +165,7 @@ class CompiledChecks:
     def sorted_search(self, keys, key_off, key_len, vals, val_off, val_len, sort, limit: int, want_first_fail=True,
                       status=None, stream=None):
         """As sorted_search (hdx_checks_sorted_device): returns what it returns."""
-        from .sorting import _sorted_search
+        from .sorting import _sorted_search  # sorting imports this module
 
         def call(ptrs, n, spec, lim, first_fail, top, count, status_ptr, stream_ptr):
             return lib().hdx_checks_sorted_device(self._handle(), *ptrs, n, spec, lim, first_fail, top, count,

@@ -439,9 +439,7 @@ hdx_status region_view(hdx_region_table_s* t, int dev, RegionView& v) {
 }
 }  // namespace hdx
 
-static hdx_status hash_encoded(const uint32_t* types, uint32_t attrs_sz, const uint8_t* keys,
-                               const uint64_t* key_off, const uint32_t* key_len, const uint8_t* vals,
-                               const uint64_t* val_off, const uint32_t* val_len, uint64_t n,
+static hdx_status hash_encoded(const uint32_t* types, uint32_t attrs_sz, const StoredObjects& so, uint64_t n,
                                const hdx_region_table* tables, uint32_t ntables, uint64_t* region_ids,
                                uint64_t* coords, uint64_t* versions, uint32_t* status_dev, hdx_stream stream) {
     std::vector<uint8_t> codes(attrs_sz ? attrs_sz : 1);
@@ -449,12 +447,11 @@ static hdx_status hash_encoded(const uint32_t* types, uint32_t attrs_sz, const u
     if (st != HDX_OK) return st;
     if ((st = check_tables(tables, ntables, attrs_sz, region_ids)) != HDX_OK) return st;
     if (n == 0) return HDX_OK;
-    if (!keys || !key_off || !key_len || !vals || !val_off || !val_len || (!coords && !ntables))
-        return fail(HDX_E_INVALID, "NULL device pointer");
+    if (!has_columns(so, SO_ALL) || (!coords && !ntables)) return fail(HDX_E_INVALID, "NULL device pointer");
     if ((st = bind_device(-1)) != HDX_OK) return st;
     EncodedArgs a;
-    if ((st = encoded_args(a, codes.data(), attrs_sz, keys, key_off, key_len, vals, val_off, val_len, n, coords,
-                           versions, status_dev, tables, ntables, region_ids, n, t_state.device)) != HDX_OK)
+    if ((st = encoded_args(a, codes.data(), attrs_sz, so, n, coords, versions, status_dev, tables, ntables, region_ids,
+                           n, t_state.device)) != HDX_OK)
         return st;
     HIP_TRY(launch_hash_encoded(a, (hipStream_t)stream));
     return HDX_OK;
@@ -466,8 +463,8 @@ HDX_EXPORT hdx_status hdx_hash_encoded_device(const uint32_t* types, uint32_t at
                                               const uint64_t* val_off, const uint32_t* val_len,
                                               uint64_t n, uint64_t* coords, uint64_t* versions,
                                               uint32_t* status_dev, hdx_stream stream) {
-    return hash_encoded(types, attrs_sz, keys, key_off, key_len, vals, val_off, val_len, n, nullptr, 0, nullptr,
-                        coords, versions, status_dev, stream);
+    const StoredObjects so{keys, key_off, key_len, vals, val_off, val_len};
+    return hash_encoded(types, attrs_sz, so, n, nullptr, 0, nullptr, coords, versions, status_dev, stream);
 }
 
 HDX_EXPORT hdx_status hdx_hash_encoded_regions_device(const uint32_t* types, uint32_t attrs_sz,
@@ -479,8 +476,8 @@ HDX_EXPORT hdx_status hdx_hash_encoded_regions_device(const uint32_t* types, uin
                                                       uint64_t* versions, uint32_t* status_dev,
                                                       hdx_stream stream) {
     if (ntables == 0) return fail(HDX_E_INVALID, "no region tables");
-    return hash_encoded(types, attrs_sz, keys, key_off, key_len, vals, val_off, val_len, n, tables, ntables,
-                        region_ids, coords, versions, status_dev, stream);
+    const StoredObjects so{keys, key_off, key_len, vals, val_off, val_len};
+    return hash_encoded(types, attrs_sz, so, n, tables, ntables, region_ids, coords, versions, status_dev, stream);
 }
 
 namespace hdx {
@@ -523,20 +520,13 @@ hdx_status batch_args(BatchArgs& args, const uint8_t* codes, uint32_t A, const u
     return HDX_OK;
 }
 
-hdx_status encoded_args(EncodedArgs& a, const uint8_t* codes, uint32_t A, const uint8_t* keys,
-                        const uint64_t* key_off, const uint32_t* key_len, const uint8_t* vals,
-                        const uint64_t* val_off, const uint32_t* val_len, uint64_t n, uint64_t* coords,
-                        uint64_t* versions, uint32_t* status, const hdx_region_table* tables, uint32_t T,
-                        uint64_t* ids, uint64_t ids_stride, int dev) {
+hdx_status encoded_args(EncodedArgs& a, const uint8_t* codes, uint32_t A, const StoredObjects& so, uint64_t n,
+                        uint64_t* coords, uint64_t* versions, uint32_t* status, const hdx_region_table* tables,
+                        uint32_t T, uint64_t* ids, uint64_t ids_stride, int dev) {
     a = EncodedArgs{};
     hdx_status st = set_codes(a, codes, A);
     if (st != HDX_OK) return st;
-    a.keys = keys;
-    a.key_off = key_off;
-    a.key_len = key_len;
-    a.vals = vals;
-    a.val_off = val_off;
-    a.val_len = val_len;
+    static_cast<StoredObjects&>(a) = so;
     a.coords = coords;
     a.versions = versions;
     a.status = status;

@@ -1,7 +1,10 @@
 // hdx_capi_index.cpp — C-ABI for the index-key encoders and the search
 // region test (include/hdxhash.h).  Host work here is argument
 // checking and packing the search endpoints; the hashing and the per-region
-// tests run in hdx_index.hip / hdx_kernels.hip.
+// tests run in hdx_index.hip / hdx_kernels.hip.  The stored-object entry
+// points (index entries, checks, sorted search, gather) each build one
+// StoredObjects (hdx_host_common.h) from their parameters; the helpers
+// behind them take that view.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -137,17 +140,15 @@ HDX_EXPORT hdx_status hdx_index_entries_plan_device(const uint32_t* types, uint3
                                                     const hdx_index_spec* specs, uint32_t m, uint32_t* attr_off,
                                                     uint32_t* attr_len, uint64_t* entry_off, uint32_t* status_dev,
                                                     hdx_stream stream) {
+    const StoredObjects so{nullptr, nullptr, key_len, vals, val_off, val_len};
     IndexEntriesArgs a;
     hdx_status st = entries_args(a, types, attrs_sz, specs, m);
     if (st != HDX_OK) return st;
-    if (!key_len || !vals || !val_off || !val_len || !attr_off || !attr_len || !entry_off)
+    if (!has_columns(so, SO_KEY_LEN | SO_VALS | SO_VAL_OFF | SO_VAL_LEN) || !attr_off || !attr_len || !entry_off)
         return fail(HDX_E_INVALID, "NULL device pointer");
     if (n > (UINT64_MAX >> 8) / m) return fail(HDX_E_INVALID, "n * m overflows");
     if ((st = bind_device(-1)) != HDX_OK) return st;
-    a.key_len = key_len;
-    a.vals = vals;
-    a.val_off = val_off;
-    a.val_len = val_len;
+    static_cast<StoredObjects&>(a) = so;
     a.attr_off = attr_off;
     a.attr_len = attr_len;
     a.entry_off = entry_off;
@@ -167,18 +168,15 @@ HDX_EXPORT hdx_status hdx_index_entries_fill_device(const uint32_t* types, uint3
                                                     const uint64_t* entry_off, uint8_t* entries,
                                                     uint64_t entries_bytes, uint32_t* status_dev,
                                                     hdx_stream stream) {
+    const StoredObjects so{keys, key_off, key_len, vals, val_off, nullptr};
     IndexEntriesArgs a;
     hdx_status st = entries_args(a, types, attrs_sz, specs, m);
     if (st != HDX_OK) return st;
-    if (!keys || !key_off || !key_len || !vals || !val_off || !attr_off || !attr_len || !entry_off || !entries)
+    if (!has_columns(so, SO_ALL & ~SO_VAL_LEN) || !attr_off || !attr_len || !entry_off || !entries)
         return fail(HDX_E_INVALID, "NULL device pointer");
     if (n > (UINT64_MAX >> 8) / m) return fail(HDX_E_INVALID, "n * m overflows");
     if ((st = bind_device(-1)) != HDX_OK) return st;
-    a.keys = keys;
-    a.key_off = key_off;
-    a.key_len = key_len;
-    a.vals = vals;
-    a.val_off = val_off;
+    static_cast<StoredObjects&>(a) = so;
     a.attr_off = const_cast<uint32_t*>(attr_off);
     a.attr_len = const_cast<uint32_t*>(attr_len);
     a.entry_off = const_cast<uint64_t*>(entry_off);
@@ -198,36 +196,22 @@ namespace {
 
 // The stored objects, and the STRING comparisons' constants, each at its op's
 // 8-byte-aligned offset (a.konst is zeroed), of a compiled list of checks.
-void check_objects(CheckArgs& a, const hdx_attribute_check* checks, uint32_t c, const uint8_t* keys,
-                   const uint64_t* key_off, const uint32_t* key_len, const uint8_t* vals, const uint64_t* val_off,
-                   const uint32_t* val_len) {
+void check_objects(CheckArgs& a, const hdx_attribute_check* checks, uint32_t c, const StoredObjects& so) {
     for (uint32_t k = 0; k < c; ++k)
         if (a.op[k].op != OP_NEVER && a.op[k].op < OP_LEN_EQ && a.op[k].family == FAM_STRING && a.op[k].klen)
             std::memcpy(reinterpret_cast<uint8_t*>(a.konst) + a.op[k].koff, checks[k].value, a.op[k].klen);
-    a.keys = keys;
-    a.key_off = key_off;
-    a.key_len = key_len;
-    a.vals = vals;
-    a.val_off = val_off;
-    a.val_len = val_len;
+    static_cast<StoredObjects&>(a) = so;
 }
-
-}  // namespace
-
-namespace {
 
 // Both forms behind their compile step: a.op holds the ops; rx: NULL or the compiled list's programs.
 hdx_status check_encoded_run(CheckArgs& a, const RegexArgs* rx, uint32_t attrs_sz, const hdx_attribute_check* checks,
-                             uint32_t c, const uint8_t* keys, const uint64_t* key_off, const uint32_t* key_len,
-                             const uint8_t* vals, const uint64_t* val_off, const uint32_t* val_len, uint64_t n,
-                             uint32_t* first_fail, uint64_t* match, uint64_t* match_count, uint32_t* status_dev,
-                             hdx_stream stream) {
-    if (!keys || !key_off || !key_len || !vals || !val_off || !val_len || !first_fail)
-        return fail(HDX_E_INVALID, "NULL device pointer");
+                             uint32_t c, const StoredObjects& so, uint64_t n, uint32_t* first_fail, uint64_t* match,
+                             uint64_t* match_count, uint32_t* status_dev, hdx_stream stream) {
+    if (!has_columns(so, SO_ALL) || !first_fail) return fail(HDX_E_INVALID, "NULL device pointer");
     if (match && !match_count) return fail(HDX_E_INVALID, "match without match_count");
     hdx_status st = bind_device(-1);
     if (st != HDX_OK) return st;
-    check_objects(a, checks, c, keys, key_off, key_len, vals, val_off, val_len);
+    check_objects(a, checks, c, so);
     a.first_fail = first_fail;
     a.match = match;
     a.match_count = match_count;
@@ -258,11 +242,11 @@ HDX_EXPORT hdx_status hdx_check_encoded_device(const uint32_t* types, uint32_t a
                                                const hdx_attribute_check* checks, uint32_t c,
                                                uint32_t* first_fail, uint64_t* match, uint64_t* match_count,
                                                uint32_t* status_dev, hdx_stream stream) {
+    const StoredObjects so{keys, key_off, key_len, vals, val_off, val_len};
     CheckArgs a{};
     const hdx_status st = compile_checks(types, attrs_sz, checks, c, HDX_CHECK_BYTES_MAX, a.op);
     if (st != HDX_OK) return st;
-    return check_encoded_run(a, nullptr, attrs_sz, checks, c, keys, key_off, key_len, vals, val_off, val_len, n,
-                             first_fail, match, match_count, status_dev, stream);
+    return check_encoded_run(a, nullptr, attrs_sz, checks, c, so, n, first_fail, match, match_count, status_dev, stream);
 }
 
 HDX_EXPORT hdx_status hdx_checks_encoded_device(hdx_checks h, const uint8_t* keys, const uint64_t* key_off,
@@ -270,12 +254,13 @@ HDX_EXPORT hdx_status hdx_checks_encoded_device(hdx_checks h, const uint8_t* key
                                                 const uint64_t* val_off, const uint32_t* val_len, uint64_t n,
                                                 uint32_t* first_fail, uint64_t* match, uint64_t* match_count,
                                                 uint32_t* status_dev, hdx_stream stream) {
+    const StoredObjects so{keys, key_off, key_len, vals, val_off, val_len};
     if (!h) return fail(HDX_E_INVALID, "the compiled list is NULL");
     CheckArgs a{};
     RegexArgs rx;
     compiled_args(h, a.op, rx);
-    return check_encoded_run(a, &rx, h->attrs_sz, h->checks, h->c, keys, key_off, key_len, vals, val_off, val_len, n,
-                             first_fail, match, match_count, status_dev, stream);
+    return check_encoded_run(a, &rx, h->attrs_sz, h->checks, h->c, so, n, first_fail, match, match_count, status_dev,
+                             stream);
 }
 
 // ---- the top-limit matches by one attribute (hdx_sorted.hip) ---------------
@@ -286,20 +271,17 @@ namespace {
 
 // Both forms behind their compile step, as check_encoded_run.
 hdx_status sorted_search_run(SortedArgs& a, const RegexArgs* rx, const uint32_t* types, uint32_t attrs_sz,
-                             const hdx_attribute_check* checks, uint32_t c, const uint8_t* keys,
-                             const uint64_t* key_off, const uint32_t* key_len, const uint8_t* vals,
-                             const uint64_t* val_off, const uint32_t* val_len, uint64_t n, const hdx_sort_spec* sort,
-                             uint64_t limit, uint32_t* first_fail, uint64_t* top, uint64_t* top_count,
-                             uint32_t* status_dev, hdx_stream stream) {
+                             const hdx_attribute_check* checks, uint32_t c, const StoredObjects& so, uint64_t n,
+                             const hdx_sort_spec* sort, uint64_t limit, uint32_t* first_fail, uint64_t* top,
+                             uint64_t* top_count, uint32_t* status_dev, hdx_stream stream) {
     int fam;
     hdx_status st = sort_args(types, attrs_sz, sort, &fam);
     if (st != HDX_OK) return st;
     if (limit > HDX_SORT_LIMIT_MAX)
         return fail(HDX_E_INVALID, "limit=%llu above %d", (unsigned long long)limit, HDX_SORT_LIMIT_MAX);
-    if (!keys || !key_off || !key_len || !vals || !val_off || !val_len || !top || !top_count)
-        return fail(HDX_E_INVALID, "NULL device pointer");
+    if (!has_columns(so, SO_ALL) || !top || !top_count) return fail(HDX_E_INVALID, "NULL device pointer");
     if ((st = bind_device(-1)) != HDX_OK) return st;
-    check_objects(a.ck, checks, c, keys, key_off, key_len, vals, val_off, val_len);
+    check_objects(a.ck, checks, c, so);
     a.ck.first_fail = first_fail;
     a.ck.status = status_dev;
     a.ck.n = n;
@@ -329,11 +311,12 @@ HDX_EXPORT hdx_status hdx_sorted_search_device(const uint32_t* types, uint32_t a
                                                const hdx_sort_spec* sort, uint64_t limit, uint32_t* first_fail,
                                                uint64_t* top, uint64_t* top_count, uint32_t* status_dev,
                                                hdx_stream stream) {
+    const StoredObjects so{keys, key_off, key_len, vals, val_off, val_len};
     SortedArgs a{};
     const hdx_status st = compile_checks(types, attrs_sz, checks, c, HDX_CHECK_BYTES_MAX, a.ck.op);
     if (st != HDX_OK) return st;
-    return sorted_search_run(a, nullptr, types, attrs_sz, checks, c, keys, key_off, key_len, vals, val_off, val_len, n,
-                             sort, limit, first_fail, top, top_count, status_dev, stream);
+    return sorted_search_run(a, nullptr, types, attrs_sz, checks, c, so, n, sort, limit, first_fail, top, top_count,
+                             status_dev, stream);
 }
 
 HDX_EXPORT hdx_status hdx_checks_sorted_device(hdx_checks h, const uint8_t* keys, const uint64_t* key_off,
@@ -341,12 +324,13 @@ HDX_EXPORT hdx_status hdx_checks_sorted_device(hdx_checks h, const uint8_t* keys
                                                const uint32_t* val_len, uint64_t n, const hdx_sort_spec* sort,
                                                uint64_t limit, uint32_t* first_fail, uint64_t* top,
                                                uint64_t* top_count, uint32_t* status_dev, hdx_stream stream) {
+    const StoredObjects so{keys, key_off, key_len, vals, val_off, val_len};
     if (!h) return fail(HDX_E_INVALID, "the compiled list is NULL");
     SortedArgs a{};
     RegexArgs rx;
     compiled_args(h, a.ck.op, rx);
-    return sorted_search_run(a, &rx, h->types, h->attrs_sz, h->checks, h->c, keys, key_off, key_len, vals, val_off,
-                             val_len, n, sort, limit, first_fail, top, top_count, status_dev, stream);
+    return sorted_search_run(a, &rx, h->types, h->attrs_sz, h->checks, h->c, so, n, sort, limit, first_fail, top,
+                             top_count, status_dev, stream);
 }
 
 // ---- the objects behind a match or top list (hdx_gather_objects.hip) --------
@@ -356,22 +340,14 @@ HDX_EXPORT uint32_t hdx_gather_tile_bytes(void) { return kGatherTileBytes; }
 namespace {
 
 // Fill's arguments, checked; both fill forms take them.
-hdx_status gather_fill_args(GatherObjectsArgs& a, const uint8_t* keys, const uint64_t* key_off,
-                            const uint32_t* key_len, const uint8_t* vals, const uint64_t* val_off,
-                            const uint32_t* val_len, uint64_t n, const uint64_t* idx, const uint64_t* count_dev,
-                            uint64_t cap, uint32_t what, const uint64_t* rec_off, uint8_t* out, uint64_t out_bytes,
-                            uint32_t* status_dev) {
-    hdx_status st = gather_objects_check(key_len && val_len && idx && rec_off && out, true, keys, key_off, vals,
-                                         val_off, n, cap, what);
+hdx_status gather_fill_args(GatherObjectsArgs& a, const StoredObjects& so, uint64_t n, const uint64_t* idx,
+                            const uint64_t* count_dev, uint64_t cap, uint32_t what, const uint64_t* rec_off,
+                            uint8_t* out, uint64_t out_bytes, uint32_t* status_dev) {
+    hdx_status st = gather_objects_check(so, idx && rec_off && out, true, n, cap, what);
     if (st != HDX_OK) return st;
     if ((st = bind_device(-1)) != HDX_OK) return st;
     a = GatherObjectsArgs{};
-    a.keys = keys;
-    a.key_off = key_off;
-    a.key_len = key_len;
-    a.vals = vals;
-    a.val_off = val_off;
-    a.val_len = val_len;
+    static_cast<StoredObjects&>(a) = so;
     a.idx = idx;
     a.count = count_dev;
     a.rec_off = const_cast<uint64_t*>(rec_off);
@@ -390,13 +366,12 @@ HDX_EXPORT hdx_status hdx_gather_objects_plan_device(const uint32_t* key_len, co
                                                      const uint64_t* idx, const uint64_t* count_dev, uint64_t cap,
                                                      uint32_t what, uint64_t* rec_off, uint32_t* rec_key_len,
                                                      uint32_t* status_dev, hdx_stream stream) {
-    hdx_status st = gather_objects_check(key_len && val_len && idx && rec_off, false, nullptr, nullptr, nullptr,
-                                         nullptr, n, cap, what);
+    const StoredObjects so{nullptr, nullptr, key_len, nullptr, nullptr, val_len};
+    hdx_status st = gather_objects_check(so, idx && rec_off, false, n, cap, what);
     if (st != HDX_OK) return st;
     if ((st = bind_device(-1)) != HDX_OK) return st;
     GatherObjectsArgs a{};
-    a.key_len = key_len;
-    a.val_len = val_len;
+    static_cast<StoredObjects&>(a) = so;
     a.idx = idx;
     a.count = count_dev;
     a.rec_off = rec_off;
@@ -417,9 +392,9 @@ HDX_EXPORT hdx_status hdx_gather_objects_fill_device(const uint8_t* keys, const 
                                                      const uint64_t* idx, const uint64_t* count_dev, uint64_t cap,
                                                      uint32_t what, const uint64_t* rec_off, uint8_t* out,
                                                      uint64_t out_bytes, uint32_t* status_dev, hdx_stream stream) {
+    const StoredObjects so{keys, key_off, key_len, vals, val_off, val_len};
     GatherObjectsArgs a;
-    const hdx_status st = gather_fill_args(a, keys, key_off, key_len, vals, val_off, val_len, n, idx, count_dev, cap,
-                                           what, rec_off, out, out_bytes, status_dev);
+    const hdx_status st = gather_fill_args(a, so, n, idx, count_dev, cap, what, rec_off, out, out_bytes, status_dev);
     if (st != HDX_OK) return st;
     HIP_TRY(launch_gather_objects_fill(a, (hipStream_t)stream));
     return HDX_OK;
@@ -432,9 +407,9 @@ HDX_EXPORT int hdxdbg_gather_objects_fill_by_extents(const uint8_t* keys, const 
                                                      const uint64_t* idx, const uint64_t* count_dev, uint64_t cap,
                                                      uint32_t what, const uint64_t* rec_off, uint8_t* out,
                                                      uint64_t out_bytes, uint32_t* status_dev, void* stream) {
+    const StoredObjects so{keys, key_off, key_len, vals, val_off, val_len};
     GatherObjectsArgs a;
-    const hdx_status st = gather_fill_args(a, keys, key_off, key_len, vals, val_off, val_len, n, idx, count_dev, cap,
-                                           what, rec_off, out, out_bytes, status_dev);
+    const hdx_status st = gather_fill_args(a, so, n, idx, count_dev, cap, what, rec_off, out, out_bytes, status_dev);
     if (st != HDX_OK) return st;
     bool no_scratch = false;
     HIP_TRY(launch_gather_objects_by_extents(a, (hipStream_t)stream, &no_scratch));

@@ -533,13 +533,13 @@ HDX_EXPORT hdx_status hdx_sorted_search(const uint32_t* types, uint32_t attrs_sz
                                         const uint64_t* val_off, const uint32_t* val_len, uint64_t n,
                                         const hdx_attribute_check* checks, uint32_t c, const hdx_sort_spec* sort,
                                         uint64_t limit, uint64_t* top, uint64_t* top_count, uint32_t* status) {
+    const StoredObjects so{keys, key_off, key_len, vals, val_off, val_len};
     CheckOp ops[HDX_MAX_CHECKS];
     hdx_status st = compile_checks(types, attrs_sz, checks, c, UINT64_MAX, ops);
     if (st != HDX_OK) return st;
     int fam;
     if ((st = sort_args(types, attrs_sz, sort, &fam)) != HDX_OK) return st;
-    if (!keys || !key_off || !key_len || !vals || !val_off || !val_len || !top || !top_count)
-        return fail(HDX_E_INVALID, "NULL pointer");
+    if (!has_columns(so, SO_ALL) || !top || !top_count) return fail(HDX_E_INVALID, "NULL pointer");
     // the attributes the walk reports: the ops' and, last, the sort attribute
     uint32_t want[HDX_MAX_CHECKS + 1], pos[HDX_MAX_CHECKS + 1], len[HDX_MAX_CHECKS + 1];
     for (uint32_t k = 0; k < c; ++k) want[k] = ops[k].op != OP_NEVER ? ops[k].attr : 0;  // 0: never reported
@@ -609,8 +609,8 @@ HDX_EXPORT hdx_status hdx_gather_objects(const uint8_t* keys, const uint64_t* ke
                                          uint64_t n, const uint64_t* idx, uint64_t count, uint32_t what,
                                          uint64_t* rec_off, uint32_t* rec_key_len, uint8_t* out, uint64_t out_bytes,
                                          uint32_t* status) {
-    const hdx_status st = gather_objects_check(key_len && val_len && idx && rec_off && out, true, keys, key_off, vals,
-                                               val_off, n, count, what);
+    const StoredObjects so{keys, key_off, key_len, vals, val_off, val_len};
+    const hdx_status st = gather_objects_check(so, idx && rec_off && out, true, n, count, what);
     if (st != HDX_OK) return st;
     uint32_t bits = 0;
     uint64_t at = 0;

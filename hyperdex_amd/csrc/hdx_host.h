@@ -72,11 +72,9 @@ hdx_status batch_args(BatchArgs& args, const uint8_t* codes, uint32_t A, const u
                       uint32_t* status, const hdx_region_table* tables, uint32_t T, uint64_t* ids,
                       uint64_t ids_stride, int dev);
 // The same for stored objects (the sweep).
-hdx_status encoded_args(EncodedArgs& a, const uint8_t* codes, uint32_t A, const uint8_t* keys,
-                        const uint64_t* key_off, const uint32_t* key_len, const uint8_t* vals,
-                        const uint64_t* val_off, const uint32_t* val_len, uint64_t n, uint64_t* coords,
-                        uint64_t* versions, uint32_t* status, const hdx_region_table* tables, uint32_t T,
-                        uint64_t* ids, uint64_t ids_stride, int dev);
+hdx_status encoded_args(EncodedArgs& a, const uint8_t* codes, uint32_t A, const StoredObjects& so, uint64_t n,
+                        uint64_t* coords, uint64_t* versions, uint32_t* status, const hdx_region_table* tables,
+                        uint32_t T, uint64_t* ids, uint64_t ids_stride, int dev);
 // Device scratch owned by the library (per-thread staging and streams),
 // registered so hdx_shutdown can free every thread's (track_scratch /
 // untrack_scratch; release() must leave the object reusable).
@@ -186,12 +184,21 @@ struct HostRegions {
 hdx_status hash_host(const uint8_t* codes, uint32_t A, const uint8_t* blob, uint64_t blob_bytes,
                      const uint64_t* obj_base, const uint32_t* attr_len, uint64_t n, uint64_t* coords,
                      const HostRegions* R);
+// Stored objects in host memory: the columns and the sizes of the two stores, which every
+// object's extents are checked against.
+struct StoredHost {
+    StoredObjects o;
+    uint64_t keys_bytes, vals_bytes;
+    // objects [first, ...): the per-object columns advance, the stores stay
+    StoredHost from(uint64_t first) const {
+        return {{o.keys, o.key_off + first, o.key_len + first, o.vals, o.val_off + first, o.val_len + first},
+                keys_bytes, vals_bytes};
+    }
+};
 // Stored objects: *status_bits receives the OR of the device status words
 // (1 << HDX_E_BADENC, 1 << HDX_E_BADSIZE); versions may be NULL.
-hdx_status hash_encoded_host(const uint8_t* codes, uint32_t A, const uint8_t* keys, uint64_t keys_bytes,
-                             const uint64_t* key_off, const uint32_t* key_len, const uint8_t* vals,
-                             uint64_t vals_bytes, const uint64_t* val_off, const uint32_t* val_len, uint64_t n,
-                             uint64_t* coords, uint64_t* versions, const HostRegions* R, uint32_t* status_bits);
+hdx_status hash_encoded_host(const uint8_t* codes, uint32_t A, const StoredHost& h, uint64_t n, uint64_t* coords,
+                             uint64_t* versions, const HostRegions* R, uint32_t* status_bits);
 
 // The device set of hdx_init_mask (hdx_multi.cpp): create (replacing a set
 // of another mask), tear down (waits for calls in progress, joins its
@@ -202,10 +209,8 @@ void device_set_teardown();
 hdx_status hash_host_any(const uint8_t* codes, uint32_t A, const uint8_t* blob, uint64_t blob_bytes,
                          const uint64_t* obj_base, const uint32_t* attr_len, uint64_t n, uint64_t* coords,
                          const HostRegions* R);
-hdx_status hash_encoded_host_any(const uint8_t* codes, uint32_t A, const uint8_t* keys, uint64_t keys_bytes,
-                                 const uint64_t* key_off, const uint32_t* key_len, const uint8_t* vals,
-                                 uint64_t vals_bytes, const uint64_t* val_off, const uint32_t* val_len, uint64_t n,
-                                 uint64_t* coords, uint64_t* versions, const HostRegions* R);
+hdx_status hash_encoded_host_any(const uint8_t* codes, uint32_t A, const StoredHost& h, uint64_t n, uint64_t* coords,
+                                 uint64_t* versions, const HostRegions* R);
 
 }  // namespace hdx
 

@@ -70,20 +70,46 @@ inline uint64_t entry_encoded_size(uint32_t enc, uint64_t len) {
 // Sets the calling thread's hdx_last_error() text and returns s.
 hdx_status fail(hdx_status s, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 
+// n stored objects: object i's key is key_len[i] bytes at keys + key_off[i], its value val_len[i]
+// bytes at vals + val_off[i]; keys == vals for records [key][value] in one store.  Every
+// extern "C" entry point after the hash builds one from its parameters; the host layers below it
+// pass the view on, and the kernel argument structs that read stored objects derive from it
+// (hdx_internal.h), so a new stored-object call is one construction, one has_columns with its row
+// of the table, and one assignment into its arguments.  The columns each stage reads (the others
+// may be NULL):
+//   sweep, checks, sorted search   all
+//   entries plan                   key_len, vals, val_off, val_len
+//   entries fill                   keys, key_off, key_len, vals, val_off
+//   gather plan                    key_len, val_len
+//   gather fill                    key_len, val_len; keys, key_off with KEYS; vals, val_off with VALUES
+struct StoredObjects {
+    const uint8_t* keys;  const uint64_t* key_off;  const uint32_t* key_len;
+    const uint8_t* vals;  const uint64_t* val_off;  const uint32_t* val_len;
+};
+enum : uint32_t {
+    SO_KEYS = 1, SO_KEY_OFF = 2, SO_KEY_LEN = 4, SO_VALS = 8, SO_VAL_OFF = 16, SO_VAL_LEN = 32,
+    SO_ALL = 63,
+};
+// True when none of the columns in mask is NULL.
+inline bool has_columns(const StoredObjects& so, uint32_t mask) {
+    const uint32_t have = (so.keys ? SO_KEYS : 0u) | (so.key_off ? SO_KEY_OFF : 0u) | (so.key_len ? SO_KEY_LEN : 0u) |
+                          (so.vals ? SO_VALS : 0u) | (so.val_off ? SO_VAL_OFF : 0u) | (so.val_len ? SO_VAL_LEN : 0u);
+    return (mask & ~have) == 0;
+}
+
 // What hdx_gather_objects and its two device calls refuse before anything is
-// read (include/hdxhash.h): `required` is the form's other pointers ANDed
+// read (include/hdxhash.h): `others` is the form's other pointers ANDed
 // together; keys and key_off matter only with KEYS, vals and val_off only
 // with VALUES (with_bytes: the forms that copy; the plan reads lengths only).
 constexpr uint64_t kGatherMaxRecords = 1ull << 40;
-inline hdx_status gather_objects_check(bool required, bool with_bytes, const void* keys, const void* key_off,
-                                       const void* vals, const void* val_off, uint64_t n, uint64_t cap,
-                                       uint32_t what) {
+inline hdx_status gather_objects_check(const StoredObjects& so, bool others, bool with_bytes, uint64_t n,
+                                       uint64_t cap, uint32_t what) {
     if (what == 0 || (what & ~(HDX_GATHER_KEYS | HDX_GATHER_VALUES)))
         return fail(HDX_E_INVALID, "what=%u is not HDX_GATHER_KEYS, HDX_GATHER_VALUES or both", what);
-    if (!required) return fail(HDX_E_INVALID, "NULL pointer");
-    if (with_bytes && (what & HDX_GATHER_KEYS) && (!keys || !key_off))
+    if (!has_columns(so, SO_KEY_LEN | SO_VAL_LEN) || !others) return fail(HDX_E_INVALID, "NULL pointer");
+    if (with_bytes && (what & HDX_GATHER_KEYS) && !has_columns(so, SO_KEYS | SO_KEY_OFF))
         return fail(HDX_E_INVALID, "HDX_GATHER_KEYS without keys or key_off");
-    if (with_bytes && (what & HDX_GATHER_VALUES) && (!vals || !val_off))
+    if (with_bytes && (what & HDX_GATHER_VALUES) && !has_columns(so, SO_VALS | SO_VAL_OFF))
         return fail(HDX_E_INVALID, "HDX_GATHER_VALUES without vals or val_off");
     if (n > kGatherMaxRecords || cap > kGatherMaxRecords)
         return fail(HDX_E_INVALID, "n=%llu or cap=%llu above 2^40", (unsigned long long)n, (unsigned long long)cap);

@@ -14,7 +14,9 @@
 // flight; a source per kind of input (PackedSource, StoredSource) validates
 // the objects, uploads a chunk and launches its kernel.  hdx_multi.cpp splits
 // a call over the device set and runs one pipeline per device (hash_host_any /
-// hash_encoded_host_any).
+// hash_encoded_host_any).  Stored objects travel through all of it as one
+// StoredHost (hdx_host.h): the columns and the two stores' sizes; a device's
+// range and a chunk are h.from(first).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -308,50 +310,44 @@ struct PackedSource {
 struct StoredSource {
     const uint8_t* codes;
     uint32_t A;
-    const uint8_t* keys;
-    uint64_t keys_bytes;
-    const uint64_t* key_off;
-    const uint32_t* key_len;
-    const uint8_t* vals;
-    uint64_t vals_bytes;
-    const uint64_t* val_off;
-    const uint32_t* val_len;
+    StoredHost h;
     const HostRegions* R;  // may be NULL
     // records [key][value] in one store (keys == vals, a LevelDB block's
     // adjacency): one span per chunk, and the kernel sees keys == vals
-    const bool records = keys == vals;
+    const bool records = h.o.keys == h.o.vals;
     const uint32_t vstore = records ? 0 : 1;  // the values' store (hdx_chunks.h)
-    const bool keys_pinned = is_pinned(keys), vals_pinned = is_pinned(vals);
-    const bool klen_pinned = is_pinned(key_len), vlen_pinned = is_pinned(val_len);
+    const bool keys_pinned = is_pinned(h.o.keys), vals_pinned = is_pinned(h.o.vals);
+    const bool klen_pinned = is_pinned(h.o.key_len), vlen_pinned = is_pinned(h.o.val_len);
     // keys and values out of order: packed as records [key][value] in index
     // order (hdx_gather.hip from pinned stores, a host copy per object from
     // pageable ones), so the kernel sees the record layout
-    const uint8_t* const keys_dev = keys_pinned ? device_view(keys) : nullptr;
-    const uint8_t* const vals_dev = vals_pinned ? device_view(vals) : nullptr;
+    const uint8_t* const keys_dev = keys_pinned ? device_view(h.o.keys) : nullptr;
+    const uint8_t* const vals_dev = vals_pinned ? device_view(h.o.vals) : nullptr;
     const int dev = thread_device();
 
     uint32_t stores() const { return records ? 1 : 2; }
     bool device_packs() const { return keys_dev && vals_dev; }
 
     hdx_status object(uint64_t i, ObjectExtents& o) const {
-        const uint32_t kl = key_len[i];
+        const uint32_t kl = h.o.key_len[i], vl = h.o.val_len[i];
+        const uint64_t ko = h.o.key_off[i], vo = h.o.val_off[i];
         if (is_numeric_code(codes[0]) && kl != 0 && kl != 8)
             return fail(HDX_E_BADSIZE, "object %llu: numeric key of %u bytes", (unsigned long long)i, kl);
-        if (key_off[i] > keys_bytes || kl > keys_bytes - key_off[i])
+        if (ko > h.keys_bytes || kl > h.keys_bytes - ko)
             return fail(HDX_E_INVALID, "object %llu: key [%llu,+%u) outside keys of %llu bytes", (unsigned long long)i,
-                        (unsigned long long)key_off[i], kl, (unsigned long long)keys_bytes);
-        if (val_off[i] > vals_bytes || val_len[i] > vals_bytes - val_off[i])
+                        (unsigned long long)ko, kl, (unsigned long long)h.keys_bytes);
+        if (vo > h.vals_bytes || vl > h.vals_bytes - vo)
             return fail(HDX_E_INVALID, "object %llu: value [%llu,+%u) outside values of %llu bytes",
-                        (unsigned long long)i, (unsigned long long)val_off[i], val_len[i],
-                        (unsigned long long)vals_bytes);
+                        (unsigned long long)i, (unsigned long long)vo, vl, (unsigned long long)h.vals_bytes);
         o.count = 2;
-        o.ext[0] = {0, key_off[i], kl};
-        o.ext[1] = {vstore, val_off[i], val_len[i]};
+        o.ext[0] = {0, ko, kl};
+        o.ext[1] = {vstore, vo, vl};
         return HDX_OK;
     }
 
     hdx_status upload(HostSlot& sl, const Chunk& c) {
-        const uint64_t i = c.first, cnt = c.cnt, bytes = c.span ? c.hi[vstore] - c.lo[vstore] : c.payload;
+        const StoredObjects so = h.from(c.first).o;  // the chunk's objects: t = 0 .. cnt
+        const uint64_t cnt = c.cnt, bytes = c.span ? c.hi[vstore] - c.lo[vstore] : c.payload;
         const uint64_t klo = c.lo[0], vlo = c.lo[vstore], key_bytes = c.hi[0] - klo;
         const uint32_t T = R ? R->T : 0;
         const bool key_span = c.span && !records;  // the key column's span beside the values'
@@ -369,18 +365,19 @@ struct StoredSource {
         const uint8_t *src_vals = nullptr, *src_keys = nullptr;
         if (c.span) {
             for (uint64_t t = 0; t < cnt; ++t) {
-                sl.h_off.p[t] = key_off[i + t] - klo;
-                sl.h_voff.p[t] = val_off[i + t] - vlo;
+                sl.h_off.p[t] = so.key_off[t] - klo;
+                sl.h_voff.p[t] = so.val_off[t] - vlo;
             }
-            if ((st = pinned_or_staged(vals + vlo, vals_pinned, sl.h_blob, bytes, &src_vals)) != HDX_OK) return st;
-            if (key_span && (st = pinned_or_staged(keys + klo, keys_pinned, sl.h_keys, key_bytes, &src_keys)) != HDX_OK)
+            if ((st = pinned_or_staged(so.vals + vlo, vals_pinned, sl.h_blob, bytes, &src_vals)) != HDX_OK) return st;
+            if (key_span &&
+                (st = pinned_or_staged(so.keys + klo, keys_pinned, sl.h_keys, key_bytes, &src_keys)) != HDX_OK)
                 return st;
         } else {
             uint64_t at = 0;  // record t: its key at h_off, its value right after
             for (uint64_t t = 0; t < cnt; ++t) {
                 sl.h_off.p[t] = at;
-                sl.h_voff.p[t] = at + key_len[i + t];
-                at += (uint64_t)key_len[i + t] + val_len[i + t];
+                sl.h_voff.p[t] = at + so.key_len[t];
+                at += (uint64_t)so.key_len[t] + so.val_len[t];
             }
             if (gather) {  // 2 extents per object, absolute device-view sources
                 if ((st = sl.h_src.need(2 * cnt)) != HDX_OK || (st = sl.h_sz.need(2 * cnt)) != HDX_OK ||
@@ -388,25 +385,25 @@ struct StoredSource {
                     (st = sl.d_sz.need(2 * cnt)) != HDX_OK || (st = sl.d_dst.need(2 * cnt)) != HDX_OK)
                     return st;
                 for (uint64_t t = 0; t < cnt; ++t) {
-                    sl.h_src.p[2 * t] = (uint64_t)(uintptr_t)keys_dev + key_off[i + t];
-                    sl.h_sz.p[2 * t] = key_len[i + t];
+                    sl.h_src.p[2 * t] = (uint64_t)(uintptr_t)keys_dev + so.key_off[t];
+                    sl.h_sz.p[2 * t] = so.key_len[t];
                     sl.h_dst.p[2 * t] = sl.h_off.p[t];
-                    sl.h_src.p[2 * t + 1] = (uint64_t)(uintptr_t)vals_dev + val_off[i + t];
-                    sl.h_sz.p[2 * t + 1] = val_len[i + t];
+                    sl.h_src.p[2 * t + 1] = (uint64_t)(uintptr_t)vals_dev + so.val_off[t];
+                    sl.h_sz.p[2 * t + 1] = so.val_len[t];
                     sl.h_dst.p[2 * t + 1] = sl.h_voff.p[t];
                 }
             } else {  // pageable: each key and value copied into the pinned staging
                 if ((st = sl.h_blob.need(std::max<uint64_t>(bytes, 1))) != HDX_OK) return st;
                 for (uint64_t t = 0; t < cnt; ++t) {
-                    std::memcpy(sl.h_blob.p + sl.h_off.p[t], keys + key_off[i + t], key_len[i + t]);
-                    std::memcpy(sl.h_blob.p + sl.h_voff.p[t], vals + val_off[i + t], val_len[i + t]);
+                    std::memcpy(sl.h_blob.p + sl.h_off.p[t], so.keys + so.key_off[t], so.key_len[t]);
+                    std::memcpy(sl.h_blob.p + sl.h_voff.p[t], so.vals + so.val_off[t], so.val_len[t]);
                 }
                 src_vals = sl.h_blob.p;
             }
         }
         const uint32_t *src_klen, *src_vlen;
-        if ((st = pinned_or_staged(key_len + i, klen_pinned, sl.h_len, cnt, &src_klen)) != HDX_OK ||
-            (st = pinned_or_staged(val_len + i, vlen_pinned, sl.h_vlen, cnt, &src_vlen)) != HDX_OK)
+        if ((st = pinned_or_staged(so.key_len, klen_pinned, sl.h_len, cnt, &src_klen)) != HDX_OK ||
+            (st = pinned_or_staged(so.val_len, vlen_pinned, sl.h_vlen, cnt, &src_vlen)) != HDX_OK)
             return st;
         const SmallCopy small[] = {{sl.h_off.p, sl.d_off.p, cnt * 8},          {sl.h_voff.p, sl.d_voff.p, cnt * 8},
                                    {src_klen, sl.d_len.p, cnt * 4},            {src_vlen, sl.d_vlen.p, cnt * 4},
@@ -427,11 +424,10 @@ struct StoredSource {
         // a packed chunk's device layout is records; the coordinates are
         // always staged, so the regions form needs no scratch
         const uint8_t* d_keys = records || !c.span ? sl.d_blob.p : sl.d_keys.p;
+        const StoredObjects staged{d_keys, sl.d_off.p, sl.d_len.p, sl.d_blob.p, sl.d_voff.p, sl.d_vlen.p};
         EncodedArgs a;
-        const hdx_status st =
-            encoded_args(a, codes, A, d_keys, sl.d_off.p, sl.d_len.p, sl.d_blob.p, sl.d_voff.p, sl.d_vlen.p, c.cnt,
-                         sl.d_coords.p, sl.d_ver.p, sl.d_status.p, R ? R->tables : nullptr, R ? R->T : 0, sl.d_ids.p,
-                         c.cnt, dev);
+        const hdx_status st = encoded_args(a, codes, A, staged, c.cnt, sl.d_coords.p, sl.d_ver.p, sl.d_status.p,
+                                           R ? R->tables : nullptr, R ? R->T : 0, sl.d_ids.p, c.cnt, dev);
         if (st != HDX_OK) return st;
         HIP_TRY(launch_hash_encoded(a, sl.s));
         return HDX_OK;
@@ -450,15 +446,13 @@ hdx_status hash_host(const uint8_t* codes, uint32_t A, const uint8_t* blob, uint
     return run_chunks(slots, src, n, Outputs(A, coords, R), nullptr);
 }
 
-hdx_status hash_encoded_host(const uint8_t* codes, uint32_t A, const uint8_t* keys, uint64_t keys_bytes,
-                             const uint64_t* key_off, const uint32_t* key_len, const uint8_t* vals,
-                             uint64_t vals_bytes, const uint64_t* val_off, const uint32_t* val_len, uint64_t n,
-                             uint64_t* coords, uint64_t* versions, const HostRegions* R, uint32_t* status_bits) {
+hdx_status hash_encoded_host(const uint8_t* codes, uint32_t A, const StoredHost& h, uint64_t n, uint64_t* coords,
+                             uint64_t* versions, const HostRegions* R, uint32_t* status_bits) {
     *status_bits = 0;
     HostSlot* slots;
     const hdx_status st = thread_slots(&slots);
     if (st != HDX_OK) return st;
-    StoredSource src{codes, A, keys, keys_bytes, key_off, key_len, vals, vals_bytes, val_off, val_len, R};
+    StoredSource src{codes, A, h, R};
     return run_chunks(slots, src, n, Outputs(A, coords, R, versions), status_bits);
 }
 
@@ -498,9 +492,7 @@ HDX_EXPORT hdx_status hdx_hash_batch_regions_host(const uint32_t* types, uint32_
                          &R);
 }
 
-static hdx_status encoded_host(const uint32_t* types, uint32_t attrs_sz, const uint8_t* keys, uint64_t keys_bytes,
-                               const uint64_t* key_off, const uint32_t* key_len, const uint8_t* vals,
-                               uint64_t vals_bytes, const uint64_t* val_off, const uint32_t* val_len, uint64_t n,
+static hdx_status encoded_host(const uint32_t* types, uint32_t attrs_sz, StoredHost h, uint64_t n,
                                const hdx_region_table* tables, uint32_t ntables, uint64_t* region_ids,
                                uint64_t* coords, uint64_t* versions) {
     std::vector<uint8_t> codes(attrs_sz ? attrs_sz : 1);
@@ -508,13 +500,13 @@ static hdx_status encoded_host(const uint32_t* types, uint32_t attrs_sz, const u
     if (st != HDX_OK) return st;
     if ((st = check_tables(tables, ntables, attrs_sz, region_ids)) != HDX_OK) return st;
     if (n == 0) return HDX_OK;
-    if (!key_off || !key_len || !val_off || !val_len || (!coords && !ntables) || (!keys && keys_bytes) ||
-        (!vals && vals_bytes))
+    if (!has_columns(h.o, SO_ALL & ~(SO_KEYS | SO_VALS)) || (!coords && !ntables) || (!h.o.keys && h.keys_bytes) ||
+        (!h.o.vals && h.vals_bytes))
         return fail(HDX_E_INVALID, "NULL host pointer");
+    if (!h.o.keys) h.o.keys = &g_empty;  // a store of 0 bytes
+    if (!h.o.vals) h.o.vals = &g_empty;
     const HostRegions R{tables, ntables, region_ids, n};
-    return hash_encoded_host_any(codes.data(), attrs_sz, keys ? keys : &g_empty, keys_bytes, key_off, key_len,
-                                 vals ? vals : &g_empty, vals_bytes, val_off, val_len, n, coords, versions,
-                                 ntables ? &R : nullptr);
+    return hash_encoded_host_any(codes.data(), attrs_sz, h, n, coords, versions, ntables ? &R : nullptr);
 }
 
 HDX_EXPORT hdx_status hdx_hash_encoded_host(const uint32_t* types, uint32_t attrs_sz, const uint8_t* keys,
@@ -522,8 +514,8 @@ HDX_EXPORT hdx_status hdx_hash_encoded_host(const uint32_t* types, uint32_t attr
                                             const uint8_t* vals, uint64_t vals_bytes, const uint64_t* val_off,
                                             const uint32_t* val_len, uint64_t n, uint64_t* coords,
                                             uint64_t* versions) {
-    return encoded_host(types, attrs_sz, keys, keys_bytes, key_off, key_len, vals, vals_bytes, val_off, val_len, n,
-                        nullptr, 0, nullptr, coords, versions);
+    const StoredObjects so{keys, key_off, key_len, vals, val_off, val_len};
+    return encoded_host(types, attrs_sz, {so, keys_bytes, vals_bytes}, n, nullptr, 0, nullptr, coords, versions);
 }
 
 HDX_EXPORT hdx_status hdx_hash_encoded_regions_host(const uint32_t* types, uint32_t attrs_sz, const uint8_t* keys,
@@ -533,6 +525,6 @@ HDX_EXPORT hdx_status hdx_hash_encoded_regions_host(const uint32_t* types, uint3
                                                     const hdx_region_table* tables, uint32_t ntables,
                                                     uint64_t* region_ids, uint64_t* coords, uint64_t* versions) {
     if (ntables == 0) return fail(HDX_E_INVALID, "no region tables");
-    return encoded_host(types, attrs_sz, keys, keys_bytes, key_off, key_len, vals, vals_bytes, val_off, val_len, n,
-                        tables, ntables, region_ids, coords, versions);
+    const StoredObjects so{keys, key_off, key_len, vals, val_off, val_len};
+    return encoded_host(types, attrs_sz, {so, keys_bytes, vals_bytes}, n, tables, ntables, region_ids, coords, versions);
 }

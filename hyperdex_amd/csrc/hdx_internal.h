@@ -47,7 +47,7 @@ struct BatchArgs {
     uint8_t codes[kKernargCodes];
     // fused region lookup (hash_regroup_regions_kernel): T tables, K whole
     // objects per wave, lds_tables u64 words of LDS table copies per workgroup
-    uint32_t T, K, lds_tables, win_bytes;  // win_bytes: unused (the retired staged kernels' LDS window)
+    uint32_t T, K, lds_tables;
     SweepTable t[kMaxSweepTables];
     // The wave-staged kernel's slot plan (hdx_wstage.h, PLAN; filled by its
     // launcher): every wave holds K objects of the same schema, so slot s of
@@ -147,16 +147,14 @@ hipError_t launch_lookup_regions_multi(const MultiRegionArgs& a, hipStream_t str
 
 // Host: the interval index of a region table, hdx_region_index.h.
 
+// The stored-object stages' arguments begin with the objects themselves (StoredObjects,
+// hdx_host_common.h, which also says which columns each stage reads); the host sets them
+// with one assignment, static_cast<StoredObjects&>(a) = so.
+//
 // Stored-object sweep (hdx_encoded.hip): device arrays.  T region tables
 // (hdx_hash_encoded_regions_device): table t's region id of object i goes to
 // t[t].out[i]; coords may then be NULL.
-struct EncodedArgs {
-    const uint8_t* keys;
-    const uint64_t* key_off;
-    const uint32_t* key_len;
-    const uint8_t* vals;
-    const uint64_t* val_off;
-    const uint32_t* val_len;
+struct EncodedArgs : StoredObjects {
     uint64_t* coords;
     uint64_t* versions;  // may be NULL
     uint32_t* status;    // may be NULL
@@ -235,13 +233,7 @@ uint64_t scan_scratch_words(uint64_t N);
 // index encoder of each indexed attribute and of the key (ENC_*,
 // hdx_host_common.h).
 constexpr uint32_t kIndexPrefixStride = 24; // >= HDX_INDEX_PREFIX_MAX
-struct IndexEntriesArgs {
-    const uint8_t* keys;      // fill only
-    const uint64_t* key_off;  // fill only
-    const uint32_t* key_len;
-    const uint8_t* vals;
-    const uint64_t* val_off;
-    const uint32_t* val_len;  // plan only
+struct IndexEntriesArgs : StoredObjects {
     uint32_t* attr_off;       // [n*m] plan writes, fill reads
     uint32_t* attr_len;       // [n*m]
     uint64_t* entry_off;      // [n*m + 1]
@@ -256,6 +248,7 @@ struct IndexEntriesArgs {
     uint8_t plen[HDX_MAX_INDICES];
     uint8_t prefix[HDX_MAX_INDICES * kIndexPrefixStride];
 };
+static_assert(sizeof(IndexEntriesArgs) == 1016, "kernel argument layout");
 // The walk (a lane per object), then scan_exclusive over the n*m + 1 entry
 // sizes.  Its block sums come from the library's stream-ordered pool
 // (PoolScratch); if that allocation fails nothing is launched and *no_scratch
@@ -267,13 +260,7 @@ hipError_t launch_index_entries_fill(const IndexEntriesArgs& a, hipStream_t stre
 // record r = [key of idx[r] if KEYS][value of idx[r] if VALUES] at out +
 // rec_off[r], r < min(*count, cap).
 constexpr uint32_t kGatherTileBytes = 4096;  // output bytes a wave of the fill owns per step
-struct GatherObjectsArgs {
-    const uint8_t* keys;      // fill only
-    const uint64_t* key_off;  // fill only
-    const uint32_t* key_len;
-    const uint8_t* vals;      // fill only
-    const uint64_t* val_off;  // fill only
-    const uint32_t* val_len;  // plan only
+struct GatherObjectsArgs : StoredObjects {
     const uint64_t* idx;      // [cap]
     const uint64_t* count;    // one u64, or NULL: cap
     uint64_t* rec_off;        // [cap + 1] plan writes, fill reads
@@ -284,6 +271,7 @@ struct GatherObjectsArgs {
     uint64_t n, cap;
     uint32_t what;            // HDX_GATHER_KEYS | HDX_GATHER_VALUES
 };
+static_assert(sizeof(GatherObjectsArgs) == 128, "kernel argument layout");
 // A lane per record stores its size, then scan_exclusive over cap + 1
 // elements; block sums from the pool, *no_scratch as above.
 hipError_t launch_gather_objects_plan(const GatherObjectsArgs& a, hipStream_t stream, bool* no_scratch);
@@ -297,13 +285,7 @@ hipError_t launch_gather_objects_by_extents(const GatherObjectsArgs& a, hipStrea
 // of compile_checks (hdx_host_common.h) and their STRING constants, packed
 // at op[k].koff, travel by value.
 constexpr uint32_t kCheckBlock = 256;  // objects per workgroup of both kernels
-struct CheckArgs {
-    const uint8_t* keys;
-    const uint64_t* key_off;
-    const uint32_t* key_len;
-    const uint8_t* vals;
-    const uint64_t* val_off;
-    const uint32_t* val_len;
+struct CheckArgs : StoredObjects {
     uint32_t* first_fail;  // [n]
     uint64_t* match;       // [n] or NULL: no compaction
     uint64_t* match_count;
@@ -313,6 +295,7 @@ struct CheckArgs {
     CheckOp op[HDX_MAX_CHECKS];
     uint64_t konst[kCheckConstBytes / 8];
 };
+static_assert(sizeof(CheckArgs) == 1632, "kernel argument layout");
 // The programs of a compiled list's OP_REGEX ops (op k's: prog[op[k].koff]):
 // a further, last kernel argument of the kernels that run them, so the kernels
 // the one-shot entry points launch keep their arguments.  Their byte-class tables
@@ -343,6 +326,7 @@ struct SortedArgs {
     uint32_t kind;        // SORT_*: SORT_TIE where attr >= attrs_sz, every object ties
     uint32_t keep, descending;
 };
+static_assert(sizeof(SortedArgs) == 1672, "kernel argument layout");
 // Device scratch of sorted_scratch_bytes(n) from the library's stream-ordered
 // pool; if that allocation fails nothing is launched and *no_scratch is set.
 uint64_t sorted_scratch_bytes(uint64_t n);

@@ -354,14 +354,11 @@ hdx_status hash_host_any(const uint8_t* codes, uint32_t A, const uint8_t* blob, 
 // One range of stored objects: the pipeline, then its status words as a
 // status (a mis-sized numeric before an undecodable value: the reference
 // asserts on the former).
-static hdx_status encoded_range(const uint8_t* codes, uint32_t A, const uint8_t* keys, uint64_t keys_bytes,
-                                const uint64_t* key_off, const uint32_t* key_len, const uint8_t* vals,
-                                uint64_t vals_bytes, const uint64_t* val_off, const uint32_t* val_len, uint64_t f,
-                                uint64_t cnt, uint64_t* coords, uint64_t* versions, const HostRegions* R) {
+static hdx_status encoded_range(const uint8_t* codes, uint32_t A, const StoredHost& h, uint64_t f, uint64_t cnt,
+                                uint64_t* coords, uint64_t* versions, const HostRegions* R) {
     uint32_t bits = 0;
     const HostRegions Rk = range_regions(R, f);
-    hdx_status st = hash_encoded_host(codes, A, keys, keys_bytes, key_off + f, key_len + f, vals, vals_bytes,
-                                      val_off + f, val_len + f, cnt, coords ? coords + f * A : nullptr,
+    hdx_status st = hash_encoded_host(codes, A, h.from(f), cnt, coords ? coords + f * A : nullptr,
                                       versions ? versions + f : nullptr, R ? &Rk : nullptr, &bits);
     if (st != HDX_OK) return st;
     if (bits & (1u << HDX_E_BADSIZE))
@@ -373,25 +370,20 @@ static hdx_status encoded_range(const uint8_t* codes, uint32_t A, const uint8_t*
     return HDX_OK;
 }
 
-hdx_status hash_encoded_host_any(const uint8_t* codes, uint32_t A, const uint8_t* keys, uint64_t keys_bytes,
-                                 const uint64_t* key_off, const uint32_t* key_len, const uint8_t* vals,
-                                 uint64_t vals_bytes, const uint64_t* val_off, const uint32_t* val_len, uint64_t n,
-                                 uint64_t* coords, uint64_t* versions, const HostRegions* R) {
+hdx_status hash_encoded_host_any(const uint8_t* codes, uint32_t A, const StoredHost& h, uint64_t n, uint64_t* coords,
+                                 uint64_t* versions, const HostRegions* R) {
     std::unique_ptr<SetRef> ref = acquire_set();
     DeviceSet* ds = ref->get();
-    if (!ds)
-        return encoded_range(codes, A, keys, keys_bytes, key_off, key_len, vals, vals_bytes, val_off, val_len, 0, n,
-                             coords, versions, R);
+    if (!ds) return encoded_range(codes, A, h, 0, n, coords, versions, R);
     std::vector<uint64_t> first;
-    hdx_status st = set_cuts(ds, StoredSizes{key_len, val_len}, n, first);
+    hdx_status st = set_cuts(ds, StoredSizes{h.o.key_len, h.o.val_len}, n, first);
     if (st != HDX_OK) return st;
     return run_on_set(ds, [&](size_t k) -> hdx_status {
         const uint64_t f = first[k], cnt = first[k + 1] - first[k];
         if (cnt == 0) return HDX_OK;
         hdx_status s = bind_device(ds->devs[k]);
         if (s != HDX_OK) return s;
-        return encoded_range(codes, A, keys, keys_bytes, key_off, key_len, vals, vals_bytes, val_off, val_len, f, cnt,
-                             coords, versions, R);
+        return encoded_range(codes, A, h, f, cnt, coords, versions, R);
     });
 }
 

@@ -11,6 +11,7 @@ the output is a stored-object batch again (batch_of), valid input to every *_enc
 import numpy as np
 
 from ._lib import HDX_E_NOMEM, check, lib
+from ._tensors import check_stored, opt_ptr, ptrs, read_back, stored_host, torch_stream
 
 KEYS = 1
 VALUES = 2
@@ -27,41 +28,30 @@ def gather_objects_plan(key_len, val_len, idx, count=None, what=KEYS | VALUES, s
     the total."""
     import torch
 
-    from .index import _torch_stream
-
-    dev = idx.device
-    n, cap = val_len.numel(), idx.numel()
-    for x in (key_len, val_len, idx) + ((count,) if count is not None else ()):
-        assert x.is_cuda and x.is_contiguous()
-    assert key_len.numel() == n and idx.element_size() == 8 and (count is None or count.element_size() == 8)
-    s = _torch_stream(stream, dev)
+    n, dev = check_stored(None, None, key_len, None, None, val_len)
+    cap = idx.numel()
+    for x in (idx,) + ((count,) if count is not None else ()):
+        assert x.is_cuda and x.is_contiguous() and x.element_size() == 8 and x.device == dev
+    s = torch_stream(stream, dev)
     with torch.cuda.stream(s):
         rec_off = torch.empty(cap + 1, dtype=torch.int64, device=dev)
         rec_key_len = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
-    # tensors without elements have no address: rec_off stands in for them; nothing reads it then
-    key_len, val_len, idx = [x if x.numel() else rec_off for x in (key_len, val_len, idx)]
-    check(lib().hdx_gather_objects_plan_device(
-        key_len.data_ptr(), val_len.data_ptr(), n, idx.data_ptr(), count.data_ptr() if count is not None else None,
-        cap, what, rec_off.data_ptr(), rec_key_len.data_ptr(), status.data_ptr() if status is not None else None,
-        s.cuda_stream))
+    key_len, val_len, idx = ptrs((key_len, val_len, idx), rec_off)
+    check(lib().hdx_gather_objects_plan_device(key_len, val_len, n, idx, opt_ptr(count), cap, what, rec_off.data_ptr(),
+                                               rec_key_len.data_ptr(), opt_ptr(status), s.cuda_stream))
     return rec_off, rec_key_len[:cap]
 
 
 def _fill(entry, keys, key_off, key_len, vals, val_off, val_len, idx, count, what, rec_off, out, status, stream):
     """One of the two fill forms (the product's, or the debug library's record-major baseline)."""
-    from .index import _torch_stream
-
-    n, cap = val_len.numel(), idx.numel()
-    for x in (keys, key_off, key_len, vals, val_off, val_len, idx, rec_off, out):
+    n, dev = check_stored(keys, key_off, key_len, vals, val_off, val_len)
+    cap = idx.numel()
+    for x in (idx, rec_off, out):
         assert x.is_cuda and x.is_contiguous()
     assert out.element_size() == 1 and rec_off.numel() == cap + 1
-    s = _torch_stream(stream, idx.device)
-    keys, key_off, key_len, vals, val_off, val_len, idx, dst = [
-        x if x.numel() else rec_off for x in (keys, key_off, key_len, vals, val_off, val_len, idx, out)]
-    check(entry(keys.data_ptr(), key_off.data_ptr(), key_len.data_ptr(), vals.data_ptr(), val_off.data_ptr(),
-                val_len.data_ptr(), n, idx.data_ptr(), count.data_ptr() if count is not None else None, cap, what,
-                rec_off.data_ptr(), dst.data_ptr(), out.numel(), status.data_ptr() if status is not None else None,
-                s.cuda_stream))
+    *cols, idx_ptr, dst = ptrs((keys, key_off, key_len, vals, val_off, val_len, idx, out), rec_off)
+    check(entry(*cols, n, idx_ptr, opt_ptr(count), cap, what, rec_off.data_ptr(), dst, out.numel(), opt_ptr(status),
+                torch_stream(stream, dev).cuda_stream))
     return out
 
 
@@ -82,16 +72,11 @@ def gather_objects(keys, key_off, key_len, vals, val_off, val_len, idx, count=No
     (status: HDX_E_INVALID's bit)."""
     import torch
 
-    from .index import _torch_stream
-
-    dev = idx.device
-    s = _torch_stream(stream, dev)
+    _, dev = check_stored(keys, key_off, key_len, vals, val_off, val_len)
+    s = torch_stream(stream, dev)
     rec_off, rec_key_len = gather_objects_plan(key_len, val_len, idx, count, what, status, s)
+    total = read_back(rec_off[-1:], s)
     with torch.cuda.stream(s):
-        host = torch.empty(1, dtype=torch.int64, pin_memory=True)
-        host.copy_(rec_off[-1:], non_blocking=True)
-        s.synchronize()
-        total = int(host.item())
         out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
     gather_objects_fill(keys, key_off, key_len, vals, val_off, val_len, idx, count, what, rec_off, out[:total],
                         status, s)
@@ -115,11 +100,9 @@ def gather_objects_host(keys, key_off, key_len, vals, val_off, val_len, idx, wha
     """hdx_gather_objects over numpy arrays on the host CPU.  Returns (out u8[total], rec_off
     u64[count + 1], rec_key_len u32[count], status bits).  With `out` given (a uint8 array) the
     records go there; if it is too small nothing is written and the bits hold HDX_E_NOMEM's."""
-    keys, vals = [None if x is None else np.ascontiguousarray(x, np.uint8) for x in (keys, vals)]
-    key_off, val_off = [None if x is None else np.ascontiguousarray(x, np.uint64) for x in (key_off, val_off)]
-    key_len, val_len = [np.ascontiguousarray(x, np.uint32) for x in (key_len, val_len)]
+    *cols, n = stored_host(keys, key_off, key_len, vals, val_off, val_len)
     idx = np.ascontiguousarray(idx, np.uint64)
-    n, count = len(val_len), len(idx)
+    count = len(idx)
     rec_off = np.zeros(count + 1, np.uint64)
     rec_key_len = np.zeros(max(count, 1), np.uint32)
     status = np.zeros(1, np.uint32)
@@ -128,9 +111,8 @@ def gather_objects_host(keys, key_off, key_len, vals, val_off, val_len, idx, wha
         return None if x is None else x.ctypes.data
 
     def call(buf, room):
-        return lib().hdx_gather_objects(ptr(keys), ptr(key_off), ptr(key_len), ptr(vals), ptr(val_off), ptr(val_len),
-                                        n, ptr(idx), count, what, ptr(rec_off), ptr(rec_key_len), ptr(buf), room,
-                                        ptr(status))
+        return lib().hdx_gather_objects(*[ptr(x) for x in cols], n, ptr(idx), count, what, ptr(rec_off),
+                                        ptr(rec_key_len), ptr(buf), room, ptr(status))
     if out is None:  # sized from the offsets a first call without room leaves
         out = np.zeros(1, np.uint8)
         st = call(out, 0)

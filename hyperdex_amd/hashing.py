@@ -24,16 +24,12 @@ import numpy as np
 
 from . import _lib
 from ._lib import HdxError, check, lib
+from ._tensors import check_stored, opt_ptr, stored_host, torch_stream, types_array
 from .datatypes import Schema
 
 
-def _u32_array(xs):
-    arr = np.ascontiguousarray(np.asarray(xs, dtype=np.uint32))
-    return arr
-
-
 def schema_check(types) -> None:
-    t = _u32_array(types)
+    t = types_array(types)
     check(lib().hdx_schema_check(t.ctypes.data, len(t)))
 
 
@@ -53,7 +49,7 @@ def _types_of(sc):
 
 
 def hash_key(sc, key: bytes) -> int:
-    t = _u32_array(_types_of(sc))
+    t = types_array(_types_of(sc))
     out = ctypes.c_uint64(0)
     buf = ctypes.create_string_buffer(bytes(key), max(len(key), 1))
     check(lib().hdx_hash_key(t.ctypes.data, len(t), buf, len(key), ctypes.byref(out)))
@@ -61,7 +57,7 @@ def hash_key(sc, key: bytes) -> int:
 
 
 def hash_object(sc, key: bytes, values: Sequence[bytes]):
-    t = _u32_array(_types_of(sc))
+    t = types_array(_types_of(sc))
     A = len(t)
     if len(values) < A - 1:
         raise HdxError(_lib.HDX_E_INVALID, "need %d values, got %d" % (A - 1, len(values)))
@@ -81,7 +77,7 @@ def hash_batch(types, blob, obj_base, attr_len, coords=None, status=None, stream
     `stream` (default: torch's current stream)."""
     import torch
 
-    t = _u32_array(types)
+    t = types_array(types)
     A = len(t)
     n = obj_base.numel()
     _check_packed(blob, obj_base, attr_len, A)
@@ -89,12 +85,9 @@ def hash_batch(types, blob, obj_base, attr_len, coords=None, status=None, stream
         coords = torch.empty((n, A), dtype=torch.int64, device=obj_base.device)
     _check_out(coords, n * A, obj_base.device, "coords")
     _check_status(status, obj_base.device)
-    if stream is None:
-        stream = torch.cuda.current_stream(obj_base.device)
-    handle = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
     check(lib().hdx_hash_batch_device(
         t.ctypes.data, A, blob.data_ptr(), obj_base.data_ptr(), attr_len.data_ptr(), n,
-        coords.data_ptr(), status.data_ptr() if status is not None else None, handle))
+        coords.data_ptr(), opt_ptr(status), torch_stream(stream, obj_base.device).cuda_stream))
     return coords
 
 
@@ -106,17 +99,6 @@ def _check_packed(blob, obj_base, attr_len, A):
         "blob / obj_base / attr_len must have 1 / 8 / 4-byte elements"
     for x in (blob, obj_base, attr_len):
         assert x.is_cuda and x.is_contiguous() and x.device == obj_base.device, "contiguous tensors on one device"
-
-
-def _check_stored(keys, key_off, key_len, vals, val_off, val_len):
-    """Stored objects: u8 keys / values, u64 offsets, u32 lengths, n of each."""
-    n = val_off.numel()
-    assert key_off.numel() == n and key_len.numel() == n and val_len.numel() == n
-    assert keys.element_size() == 1 and vals.element_size() == 1
-    assert key_off.element_size() == 8 and val_off.element_size() == 8
-    assert key_len.element_size() == 4 and val_len.element_size() == 4
-    for x in (keys, key_off, key_len, vals, val_off, val_len):
-        assert x.is_cuda and x.is_contiguous() and x.device == val_off.device
 
 
 def _check_out(x, numel, device, what):
@@ -133,7 +115,7 @@ def _check_status(status, device):
 
 def hash_batch_host(types, blob, obj_base, attr_len, out: Optional[np.ndarray] = None):
     """Host-resident batch (numpy in, numpy (n, A) uint64 out), synchronous."""
-    t = _u32_array(types)
+    t = types_array(types)
     A = len(t)
     blob = np.ascontiguousarray(blob, dtype=np.uint8)
     obj_base = np.ascontiguousarray(obj_base, dtype=np.uint64)
@@ -156,7 +138,7 @@ def hash_batch_regions_host(types, blob, obj_base, attr_len, tables, coords: boo
     """hdx_hash_batch_regions_host: host-resident batch -> region ids (T, n)
     uint64 in the RegionTables `tables` (1..4); with coords=True also the
     (n, A) coordinates.  Split over the device set like hash_batch_host."""
-    t = _u32_array(types)
+    t = types_array(types)
     A = len(t)
     blob = np.ascontiguousarray(blob, dtype=np.uint8)
     obj_base = np.ascontiguousarray(obj_base, dtype=np.uint64)
@@ -169,19 +151,6 @@ def hash_batch_regions_host(types, blob, obj_base, attr_len, tables, coords: boo
                                             obj_base.ctypes.data, attr_len.ctypes.data, n, _handles(tables),
                                             len(tables), ids.ctypes.data, out.ctypes.data if coords else None))
     return (ids, out) if coords else ids
-
-
-def _stored_host(keys, key_off, key_len, vals, val_off, val_len):
-    records = vals is keys  # one store of [key][value] records: keep it one buffer
-    keys = np.ascontiguousarray(keys, dtype=np.uint8)
-    vals = keys if records else np.ascontiguousarray(vals, dtype=np.uint8)
-    key_off = np.ascontiguousarray(key_off, dtype=np.uint64)
-    key_len = np.ascontiguousarray(key_len, dtype=np.uint32)
-    val_off = np.ascontiguousarray(val_off, dtype=np.uint64)
-    val_len = np.ascontiguousarray(val_len, dtype=np.uint32)
-    n = len(val_off)
-    assert len(key_off) == n and len(key_len) == n and len(val_len) == n
-    return keys, key_off, key_len, vals, val_off, val_len, n
 
 
 def hash_encoded_host(types, keys, key_off, key_len, vals, val_off, val_len, versions: bool = False):
@@ -200,9 +169,9 @@ def hash_encoded_host(types, keys, key_off, key_len, vals, val_off, val_len, ver
 def hash_encoded_host_status(types, keys, key_off, key_len, vals, val_off, val_len, tables=()):
     """The same, never raising for undecodable values: (coords, versions,
     status, message), plus region ids (T, n) as a 5th item with `tables`."""
-    t = _u32_array(types)
+    t = types_array(types)
     A = len(t)
-    keys, key_off, key_len, vals, val_off, val_len, n = _stored_host(keys, key_off, key_len, vals, val_off, val_len)
+    keys, key_off, key_len, vals, val_off, val_len, n = stored_host(keys, key_off, key_len, vals, val_off, val_len)
     coords = np.empty((n, A), dtype=np.uint64)
     vers = np.empty(n, dtype=np.uint64)
     kp = keys.ctypes.data if keys.size else None
@@ -233,24 +202,18 @@ def hash_encoded(types, keys, key_off, key_len, vals, val_off, val_len, coords=N
     as torch HIP tensors; returns coords (n, A) int64 (uint64 bit patterns)."""
     import torch
 
-    t = _u32_array(types)
+    t = types_array(types)
     A = len(t)
-    n = val_off.numel()
-    _check_stored(keys, key_off, key_len, vals, val_off, val_len)
+    n, dev = check_stored(keys, key_off, key_len, vals, val_off, val_len)
     if coords is None:
-        coords = torch.empty((n, A), dtype=torch.int64, device=val_off.device)
-    _check_out(coords, n * A, val_off.device, "coords")
+        coords = torch.empty((n, A), dtype=torch.int64, device=dev)
+    _check_out(coords, n * A, dev, "coords")
     if versions is not None:
-        _check_out(versions, n, val_off.device, "versions")
-    _check_status(status, val_off.device)
-    if stream is None:
-        stream = torch.cuda.current_stream(val_off.device)
-    handle = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+        _check_out(versions, n, dev, "versions")
+    _check_status(status, dev)
     check(lib().hdx_hash_encoded_device(
-        t.ctypes.data, A, keys.data_ptr(), key_off.data_ptr(), key_len.data_ptr(), vals.data_ptr(),
-        val_off.data_ptr(), val_len.data_ptr(), n, coords.data_ptr(),
-        versions.data_ptr() if versions is not None else None,
-        status.data_ptr() if status is not None else None, handle))
+        t.ctypes.data, A, *[x.data_ptr() for x in (keys, key_off, key_len, vals, val_off, val_len)], n,
+        coords.data_ptr(), opt_ptr(versions), opt_ptr(status), torch_stream(stream, dev).cuda_stream))
     return coords
 
 
@@ -262,30 +225,26 @@ def hash_encoded_regions(types, keys, key_off, key_len, vals, val_off, val_len, 
     (or a tensor to fill)."""
     import torch
 
-    t = _u32_array(types)
+    t = types_array(types)
     A = len(t)
-    n = val_off.numel()
-    _check_stored(keys, key_off, key_len, vals, val_off, val_len)
-    dev = val_off.device
-    ids = torch.empty((len(tables), n), dtype=torch.int64, device=dev)
+    n, dev = check_stored(keys, key_off, key_len, vals, val_off, val_len)
+    T = len(tables)
+    ids = torch.empty(max(T * n, 1), dtype=torch.int64, device=dev)  # never empty: an empty batch's ids need an address
     if coords is True:
         coords = torch.empty((n, A), dtype=torch.int64, device=dev)
-    if coords is not None and coords is not False:
+    elif coords is False:
+        coords = None
+    if coords is not None:
         _check_out(coords, n * A, dev, "coords")
     if versions is not None:
         _check_out(versions, n, dev, "versions")
     _check_status(status, dev)
-    handles = (ctypes.c_void_p * max(len(tables), 1))(*[tb.handle.value for tb in tables])
-    if stream is None:
-        stream = torch.cuda.current_stream(dev)
-    handle = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
     check(lib().hdx_hash_encoded_regions_device(
-        t.ctypes.data, A, keys.data_ptr(), key_off.data_ptr(), key_len.data_ptr(), vals.data_ptr(),
-        val_off.data_ptr(), val_len.data_ptr(), n, handles, len(tables), ids.data_ptr(),
-        coords.data_ptr() if coords is not None and coords is not False else None,
-        versions.data_ptr() if versions is not None else None,
-        status.data_ptr() if status is not None else None, handle))
-    return (ids, coords) if coords is not None and coords is not False else ids
+        t.ctypes.data, A, *[x.data_ptr() for x in (keys, key_off, key_len, vals, val_off, val_len)], n,
+        _handles(tables), T,
+        ids.data_ptr(), opt_ptr(coords), opt_ptr(versions), opt_ptr(status), torch_stream(stream, dev).cuda_stream))
+    ids = ids[:T * n].view(T, n)
+    return (ids, coords) if coords is not None else ids
 
 
 def hash_batch_regions(types, blob, obj_base, attr_len, tables, coords=False, status=None, stream=None):
@@ -295,7 +254,7 @@ def hash_batch_regions(types, blob, obj_base, attr_len, tables, coords=False, st
     tensor to fill)."""
     import torch
 
-    t = _u32_array(types)
+    t = types_array(types)
     A = len(t)
     n = obj_base.numel()
     _check_packed(blob, obj_base, attr_len, A)
@@ -306,20 +265,16 @@ def hash_batch_regions(types, blob, obj_base, attr_len, tables, coords=False, st
     if coords is not None and coords is not False:
         _check_out(coords, n * A, dev, "coords")
     _check_status(status, dev)
-    handles = (ctypes.c_void_p * max(len(tables), 1))(*[tb.handle.value for tb in tables])
-    if stream is None:
-        stream = torch.cuda.current_stream(dev)
-    handle = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
     check(lib().hdx_hash_batch_regions_device(
-        t.ctypes.data, A, blob.data_ptr(), obj_base.data_ptr(), attr_len.data_ptr(), n, handles, len(tables),
+        t.ctypes.data, A, blob.data_ptr(), obj_base.data_ptr(), attr_len.data_ptr(), n, _handles(tables), len(tables),
         ids.data_ptr(), coords.data_ptr() if coords is not None and coords is not False else None,
-        status.data_ptr() if status is not None else None, handle))
+        opt_ptr(status), torch_stream(stream, dev).cuda_stream))
     return (ids, coords) if coords is not None and coords is not False else ids
 
 
 def kernel_for(types, n: int):
     """(variant, kernel symbol) hash_batch would launch for this schema and n."""
-    t = _u32_array(types)
+    t = types_array(types)
     name = ctypes.c_char_p()
     v = lib().hdxdbg_kernel_for(t.ctypes.data, len(t), n, ctypes.byref(name))
     return v, (name.value or b"").decode()
@@ -332,7 +287,7 @@ def wave_geometry(types, sweep: bool = False):
     """hdxdbg_wave_geometry: what one wave of the wave-staged batch kernel
     (sweep=False) or stored-object sweep (sweep=True) holds for this schema, as
     a dict of WAVE_GEOMETRY_FIELDS; None when the schema takes another form."""
-    t = _u32_array(types)
+    t = types_array(types)
     out = np.zeros(len(WAVE_GEOMETRY_FIELDS), dtype=np.uint32)
     r = lib().hdxdbg_wave_geometry(t.ctypes.data, len(t), 1 if sweep else 0, out.ctypes.data)
     if r == -2:
@@ -383,7 +338,7 @@ def hash_batch_device_multi(types, shards, gather: bool = True, coords=None):
     coordinates.  `coords` may pass those output tensors in."""
     import torch
 
-    t = _u32_array(types)
+    t = types_array(types)
     A = len(t)
     counts = [int(s[1].numel()) for s in shards]
     N = sum(counts)
@@ -415,7 +370,7 @@ def hash_batch_regions_device_multi(types, shards, tables, gather: bool = True, 
     each shard's own (n_k, A) coordinates as a second list."""
     import torch
 
-    t = _u32_array(types)
+    t = types_array(types)
     A = len(t)
     T = len(tables)
     counts = [int(s[1].numel()) for s in shards]

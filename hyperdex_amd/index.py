@@ -12,6 +12,7 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 
 from ._lib import check, lib
+from ._tensors import check_stored, opt_ptr, ptrs, read_back, torch_stream, types_array
 from .regions import RegionTable
 
 
@@ -35,12 +36,9 @@ def index_encode(type_id: int, blob, off, length, out=None, status=None, stream=
         out = torch.empty((n, max(size, 1)), dtype=torch.uint8, device=off.device)
     assert out.is_cuda and out.is_contiguous() and out.data_ptr() % 8 == 0, \
         "out must be a contiguous device tensor at an 8-byte-aligned address"
-    if stream is None:
-        stream = torch.cuda.current_stream(off.device)
-    handle = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
     check(lib().hdx_index_encode_device(type_id, blob.data_ptr(), off.data_ptr(), length.data_ptr(), n,
-                                        out.data_ptr(), status.data_ptr() if status is not None else None,
-                                        handle))
+                                        out.data_ptr(), opt_ptr(status),
+                                        torch_stream(stream, off.device).cuda_stream))
     return out
 
 
@@ -178,43 +176,24 @@ def index_entry(spec: IndexSpec, key_type: int, key: bytes, attr_type: int, valu
     return out.raw[:need.value]
 
 
-def _torch_stream(stream, device):
-    import torch
-    if stream is None:
-        return torch.cuda.current_stream(device)
-    if hasattr(stream, "cuda_stream"):
-        return stream
-    return torch.cuda.ExternalStream(stream, device=device)
-
-
-def _types(types):
-    return np.ascontiguousarray(np.asarray(types, dtype=np.uint32))
-
-
 def index_entries_plan(types, key_len, vals, val_off, val_len, specs, status=None, stream=None):
     """hdx_index_entries_plan_device on torch HIP tensors: returns (attr_off
     i32[n*m], attr_len i32[n*m], entry_off i64[n*m + 1]) — u32 / u64 bit
     patterns; entry_off[-1] is the total size of the entries."""
     import torch
 
-    t = _types(types)
-    n, m = val_off.numel(), len(specs)
-    dev = val_off.device
-    for x in (key_len, vals, val_off, val_len):
-        assert x.is_cuda and x.is_contiguous()
-    assert val_len.numel() == n and key_len.numel() == n
-    s = _torch_stream(stream, dev)
+    t = types_array(types)
+    n, dev = check_stored(None, None, key_len, vals, val_off, val_len)
+    m = len(specs)
+    s = torch_stream(stream, dev)
     with torch.cuda.stream(s):
         attr_off = torch.empty(max(n * m, 1), dtype=torch.int32, device=dev)
         attr_len = torch.empty(max(n * m, 1), dtype=torch.int32, device=dev)
         entry_off = torch.empty(n * m + 1, dtype=torch.int64, device=dev)
-    # an empty batch is planned (and its types and specs checked) like any other: tensors without
-    # elements have no address, so entry_off stands in for them; nothing reads it when n == 0
-    key_len, vals, val_off, val_len = [x if x.numel() else entry_off for x in (key_len, vals, val_off, val_len)]
+    # an empty batch is planned (and its types and specs checked) like any other
     check(lib().hdx_index_entries_plan_device(
-        t.ctypes.data, len(t), key_len.data_ptr(), vals.data_ptr(), val_off.data_ptr(), val_len.data_ptr(), n,
-        _specs(specs), m, attr_off.data_ptr(), attr_len.data_ptr(), entry_off.data_ptr(),
-        status.data_ptr() if status is not None else None, s.cuda_stream))
+        t.ctypes.data, len(t), *ptrs((key_len, vals, val_off, val_len), entry_off), n, _specs(specs), m,
+        attr_off.data_ptr(), attr_len.data_ptr(), entry_off.data_ptr(), opt_ptr(status), s.cuda_stream))
     return attr_off[:n * m], attr_len[:n * m], entry_off
 
 
@@ -223,16 +202,16 @@ def index_entries_fill(types, keys, key_off, key_len, vals, val_off, specs, attr
     """hdx_index_entries_fill_device: writes entry e at entries[entry_off[e]:]
     (`entries` a contiguous uint8 HIP tensor, any alignment); with fewer than
     entry_off[-1] bytes nothing is written and status gets HDX_E_NOMEM's bit."""
-    t = _types(types)
-    n, m = val_off.numel(), len(specs)
-    for x in (keys, key_off, key_len, vals, val_off, attr_off, attr_len, entry_off, entries):
+    t = types_array(types)
+    n, dev = check_stored(keys, key_off, key_len, vals, val_off, None)
+    m = len(specs)
+    for x in (attr_off, attr_len, entry_off, entries):
         assert x.is_cuda and x.is_contiguous()
     assert entries.element_size() == 1 and entry_off.numel() == n * m + 1
-    s = _torch_stream(stream, val_off.device)
     check(lib().hdx_index_entries_fill_device(
-        t.ctypes.data, len(t), keys.data_ptr(), key_off.data_ptr(), key_len.data_ptr(), vals.data_ptr(),
-        val_off.data_ptr(), n, _specs(specs), m, attr_off.data_ptr(), attr_len.data_ptr(), entry_off.data_ptr(),
-        entries.data_ptr(), entries.numel(), status.data_ptr() if status is not None else None, s.cuda_stream))
+        t.ctypes.data, len(t), *[x.data_ptr() for x in (keys, key_off, key_len, vals, val_off)], n, _specs(specs), m,
+        attr_off.data_ptr(), attr_len.data_ptr(), entry_off.data_ptr(), entries.data_ptr(), entries.numel(),
+        opt_ptr(status), torch_stream(stream, dev).cuda_stream))
     return entries
 
 
@@ -246,16 +225,13 @@ def index_entries(types, keys, key_off, key_len, vals, val_off, val_len, specs, 
     HDX_E_BADSIZE bits)."""
     import torch
 
-    dev = val_off.device
-    s = _torch_stream(stream, dev)
+    n, dev = check_stored(keys, key_off, key_len, vals, val_off, val_len)
+    s = torch_stream(stream, dev)
     attr_off, attr_len, entry_off = index_entries_plan(types, key_len, vals, val_off, val_len, specs, status, s)
-    if val_off.numel() == 0:  # planned, so types and specs are checked; there is nothing to fill
+    if n == 0:  # planned, so types and specs are checked; there is nothing to fill
         return torch.empty(0, dtype=torch.uint8, device=dev), entry_off
+    total = read_back(entry_off[-1:], s)
     with torch.cuda.stream(s):
-        host = torch.empty(1, dtype=torch.int64, pin_memory=True)
-        host.copy_(entry_off[-1:], non_blocking=True)
-        s.synchronize()
-        total = int(host.item())
         entries = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
     index_entries_fill(types, keys, key_off, key_len, vals, val_off, specs, attr_off, attr_len, entry_off,
                        entries, status, s)

@@ -10,6 +10,7 @@ import ctypes
 import numpy as np
 
 from ._lib import HDX_E_BADSIZE, HdxError, check, lib
+from ._tensors import torch_stream
 
 
 class RegionTable:
@@ -57,10 +58,8 @@ def lookup_region(table: RegionTable, coords, out=None, stream=None):
     assert coords.is_cuda and coords.is_contiguous() and coords.element_size() == 8
     if out is None:
         out = torch.empty(n, dtype=torch.int64, device=coords.device)
-    if stream is None:
-        stream = torch.cuda.current_stream(coords.device)
-    handle = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
-    check(lib().hdx_lookup_region_device(table.handle, coords.data_ptr(), A, n, out.data_ptr(), handle))
+    check(lib().hdx_lookup_region_device(table.handle, coords.data_ptr(), A, n, out.data_ptr(),
+                                         torch_stream(stream, coords.device).cuda_stream))
     return out
 
 
@@ -113,10 +112,7 @@ class PointLeaders:
 
         from .hashing import hash_batch_regions
         dev = key_base.device
-        if stream is None:
-            stream = torch.cuda.current_stream(dev)
-        elif not isinstance(stream, torch.cuda.Stream):  # a raw hipStream_t handle
-            stream = torch.cuda.ExternalStream(int(stream), device=dev)
+        stream = torch_stream(stream, dev)
         with torch.cuda.stream(stream):
             status = torch.zeros(1, dtype=torch.int32, device=dev)
             ids = hash_batch_regions([key_type], blob, key_base, key_len, [self.leader, self.where],

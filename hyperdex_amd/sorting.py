@@ -19,6 +19,7 @@ from typing import Sequence
 import numpy as np
 
 from ._lib import check, lib
+from ._tensors import check_stored, opt_ptr, ptrs, read_back, stored_host, torch_stream, types_array
 from .checks import AttributeCheck, _checks
 
 HDX_SORT_LIMIT_MAX = 1024
@@ -63,16 +64,12 @@ def sorted_search_host(types, keys, key_off, key_len, vals, val_off, val_len, ch
                        sort: SortSpec, limit: int):
     """hdx_sorted_search on numpy arrays (stored objects as in hash_encoded_host):
     returns (top u64[count], status bits)."""
-    t = np.ascontiguousarray(np.asarray(types, dtype=np.uint32))
-    keys, vals = (np.ascontiguousarray(x, dtype=np.uint8) for x in (keys, vals))
-    key_off, val_off = (np.ascontiguousarray(x, dtype=np.uint64) for x in (key_off, val_off))
-    key_len, val_len = (np.ascontiguousarray(x, dtype=np.uint32) for x in (key_len, val_len))
-    n = len(val_off)
-    assert len(val_len) == n and len(key_len) == n and len(key_off) == n
+    t = types_array(types)
+    *cols, n = stored_host(keys, key_off, key_len, vals, val_off, val_len)
     top = np.empty(max(min(int(limit), n), 1), np.uint64)
     count, status, spec = ctypes.c_uint64(0), ctypes.c_uint32(0), sort._c()
     # arrays without elements still need an address: nothing reads it
-    ptr = [x.ctypes.data if x.size else top.ctypes.data for x in (keys, key_off, key_len, vals, val_off, val_len)]
+    ptr = [x.ctypes.data if x.size else top.ctypes.data for x in cols]
     check(lib().hdx_sorted_search(t.ctypes.data, len(t), *ptr, n, _checks(checks), len(checks), ctypes.byref(spec),
                                   int(limit), top.ctypes.data, ctypes.byref(count), ctypes.byref(status)))
     return top[:int(count.value)], int(status.value)
@@ -84,7 +81,7 @@ def sorted_search(types, keys, key_off, key_len, vals, val_off, val_len, checks:
     check_encoded): returns (first_fail i32[n] or None, top i64[count]).
     first_fail is check_encoded's; top holds the kept objects' indices in the
     output order.  The count is read back on `stream`, which is then waited for."""
-    t = np.ascontiguousarray(np.asarray(types, dtype=np.uint32))
+    t = types_array(types)
     arr = _checks(checks)
 
     def call(ptrs, n, spec, lim, first_fail, top, count, status_ptr, stream_ptr):
@@ -99,27 +96,13 @@ def _sorted_search(call, keys, key_off, key_len, vals, val_off, val_len, sort, l
     first_fail, top, count, status, stream) -> hdx_status."""
     import torch
 
-    from .index import _torch_stream
-
-    n = val_off.numel()
-    dev = val_off.device
-    for x in (keys, key_off, key_len, vals, val_off, val_len):
-        assert x.is_cuda and x.is_contiguous()
-    assert val_len.numel() == n and key_len.numel() == n and key_off.numel() == n
-    s = _torch_stream(stream, dev)
+    n, dev = check_stored(keys, key_off, key_len, vals, val_off, val_len)
+    s = torch_stream(stream, dev)
     with torch.cuda.stream(s):
         first_fail = torch.empty(max(n, 1), dtype=torch.int32, device=dev) if want_first_fail else None
         top = torch.empty(max(min(int(limit), HDX_SORT_LIMIT_MAX), 1), dtype=torch.int64, device=dev)
         count = torch.empty(1, dtype=torch.int64, device=dev)
-    # tensors without elements have no address: count stands in for them; nothing reads it when n == 0
-    keys, key_off, key_len, vals, val_off, val_len = [x if x.numel() else count
-                                                      for x in (keys, key_off, key_len, vals, val_off, val_len)]
     spec = sort._c()
-    check(call([x.data_ptr() for x in (keys, key_off, key_len, vals, val_off, val_len)], n, ctypes.byref(spec),
-               int(limit), first_fail.data_ptr() if want_first_fail else None, top.data_ptr(), count.data_ptr(),
-               status.data_ptr() if status is not None else None, s.cuda_stream))
-    with torch.cuda.stream(s):
-        host = torch.empty(1, dtype=torch.int64, pin_memory=True)
-        host.copy_(count, non_blocking=True)
-        s.synchronize()
-    return (first_fail[:n] if want_first_fail else None), top[:int(host.item())]
+    check(call(ptrs((keys, key_off, key_len, vals, val_off, val_len), count), n, ctypes.byref(spec), int(limit),
+               opt_ptr(first_fail), top.data_ptr(), count.data_ptr(), opt_ptr(status), s.cuda_stream))
+    return (first_fail[:n] if want_first_fail else None), top[:read_back(count, s)]
